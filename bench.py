@@ -4,6 +4,12 @@
 One "step" = zero_grad + forward + Dice/CE/SDKT loss + backward + [RCCL gradient all-reduce] + AdamW on one batch
 of synthetic patches already resident in HBM.  `python bench.py --gpus N --steps K --warmup W`; for N > 1 launch
 with torch.distributed.run (one rank per GPU).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the benchmark measures, each outside
+the timed region: CPU and eager-ROCm baselines, the per-step dispersion, the per-kernel pass with its rooflines, the communication
+diagnostics (N > 1) and, in the eval mode, the pipelined figure.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float32; inputs, weights and step count are the same from run to run, so two builds can be compared output for output --
+to round-off: the order of the kernels' atomic accumulations varies, and the training steps before the last one carry it into the weights).
 """
 import argparse
 import json
@@ -218,11 +224,22 @@ def main():
     ap.add_argument("--no-eager-baseline", action="store_true")
     ap.add_argument("--dispersion-steps", type=int, default=300, help="extra steps after the timed region whose per-step times give p10 / p50 / p90 (0 = skip)")
     ap.add_argument("--lane-probe", action="store_true", help="diagnostic: after the timed region, time dispatch-heavy kernels on every pair of tape lanes (lanes that share a dispatch pipe overlap worse)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: CPU / eager baselines, dispersion, per-kernel pass and rooflines, comm diagnostics (N > 1), "
+                                                        "the eval mode's pipelined figure (the --no-* options above then switch single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB; "
+                                                                        "fixed seeded samples of the large tensors)")
     args = ap.parse_args()
     if args.workload is None:
         args.workload = {"train": "autopet128", "eval": "autopet96", "sliding": "brats128" if args.roi == 128 else "brats96"}[args.mode]
     if args.steps is None:
         args.steps = 300 if args.mode == "train" else 0
+    if args.mode == "train" and args.steps < 1:
+        ap.error("--steps must be >= 1 in the train mode")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if not args.full:                              # a plain run: the headline only
+        args.no_cpu_baseline = args.no_eager_baseline = args.no_kernel_pass = True
+        args.dispersion_steps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))          # plain `python bench.py --gpus N`: one child process per GPU, started before anything touches HIP
@@ -267,12 +284,10 @@ def main():
     x, lab = synth(cfg, B, dev, 12345 + rank)
     eng.step(x, lab)                                           # capture (+ first step)
     # untimed pre-warm (besides the W warm-up steps): the first process on a cold box was seen 10 % below every later one (clocks, page tables,
-    # code pages); ~1.5 s of steps, never part of the timed region
-    t_pre = time.perf_counter()
-    n_pre = 0
-    while (n_pre < 150) if world > 1 else (time.perf_counter() - t_pre < 1.5 and n_pre < 400):      # (a step is a collective with world > 1: every rank the same count)
+    # code pages); ~1.5 s of steps at the headline's step time, never part of the timed region.  A fixed count (world > 1: a step is a collective, every rank
+    # the same count), not a time budget: the state the timed steps start from -- and what --dump-outputs writes -- must not depend on the box's speed
+    for n_pre in range(1, (150 if world > 1 else 400) + 1):
         eng.step()
-        n_pre += 1
         if n_pre % 16 == 0:
             torch.cuda.synchronize()
     for _ in range(max(args.warmup - 1, 0)):
@@ -296,13 +311,16 @@ def main():
     dt = float(tmax)
     loss = float(eng.loss)
     assert loss == loss, "loss is NaN"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = _dump_outputs(args.dump_outputs, _train_outputs(eng))
 
     # ---- communication diagnostics (world > 1, outside the timed region): the same step WITHOUT its collectives (every rank skips them alike), and the collectives
     # of K more steps bracketed by HIP events on the stream they are issued from.  The first multi-GPU run then says by itself whether the all-reduces are hidden:
     # exposed_ms = step - step_no_comm; per bucket: bytes, enqueue -> complete time, the stream (tape lane / comm stream) it ran on; VELOXSEG_COMM_PLACEMENT repeats
     # the run with the collectives enqueued at the other two places profiles/r03_comm_standin_probe.txt measured on one GPU
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         k2 = max(10, min(args.steps, 100))
         eng.skip_comm = True
         for _ in range(5):
@@ -396,6 +414,8 @@ def main():
                                          % _expand_split()) if args.dtype == "f32" and _expand_split() else "fp32",
                           "hip_graph": bool(eng.use_graph), "lanes_on_distinct_hw_queues": (H.query("vx_tape_lanes_distinct") if (eng.use_graph and getattr(eng, "replay_mode", "") == "tape") else None),
                           "lane_calibration_spin_us": (H.query("vx_tape_spin_us") if (eng.use_graph and getattr(eng, "replay_mode", "") == "tape") else None), "lane_on_caller_queue": (H.query("vx_tape_lane_on_caller_queue") if (eng.use_graph and getattr(eng, "replay_mode", "") == "tape") else None), "launch": (("launch tape per captured stage (csrc/tape.hip): %d kernel nodes on up to %d HIP streams, %d cross-stream dependencies (flag kernels: a store on the producing stream, a poll on the waiting one; events with VELOXSEG_TAPE_FLAGS=0)" % (sum(t.n_kernels for t in _tapes(eng)), max(t.n_lanes for t in _tapes(eng)), sum(t.n_events for t in _tapes(eng)))) if getattr(eng, "replay_mode", "") == "tape" else "hipGraph per stage") if eng.use_graph else "eager; decoder branches, encoder conv chain and per-modality PWA halves on forked HIP streams", "final_loss": round(loss, 5)}}
+    if rank == 0 and dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and comm is not None:
         out["comm"] = comm
     if rank == 0 and lane_probe is not None:
@@ -518,6 +538,54 @@ def _forward_kernel_pass(out, model, x, workload, B):
     _kernel_pass(out, prof, model, workload, B)
 
 
+DUMP_WHOLE = 1 << 22            # --dump-outputs: a tensor of up to this many elements is written whole, a larger one as a fixed seeded sample of DUMP_SAMPLE elements
+DUMP_SAMPLE = 1 << 20
+DUMP_LIMIT = 64 << 20           # bytes, all files together
+
+
+def _train_outputs(eng):
+    """what a caller of TrainEngine.step() holds after the last step: the loss, the updated weights, the step's gradients and the model's training outputs
+    (main segmentation logits; the reconstructions of the input modalities, concatenated over the channels as in VeloxSeg.assemble_train)"""
+    eng.flush()                                 # (pipelined tail: the decoder half of the update may still be running on another lane)
+    torch.cuda.synchronize()
+    res = {"loss": eng.loss.reshape(1), "params": eng.flat.param, "grads": eng.flat.grad}
+    if eng.graphs is not None:
+        seg, rec = eng._outs[0][0], [o[0] for o in eng._outs[1:]]
+    elif eng.last_outputs is not None:          # eager steps: the reference's list [pred x n, rcs, dec_pram, rc_pram x M]
+        outs, nrc = eng.last_outputs, eng.model.num_branches - 1
+        seg, rec = outs[0], [outs[len(outs) - nrc - 2]]
+    else:
+        return res
+    res["seg_logits"] = seg
+    res["reconstruction"] = rec[0] if len(rec) == 1 else torch.cat(rec, dim=1)
+    return res
+
+
+def _dump_outputs(path, arrays):
+    """arrays {name: tensor} -> path/<name>.npy, float32 (float64 stays float64); a tensor above DUMP_WHOLE elements is written as the DUMP_SAMPLE elements at
+    sorted indices drawn from a generator seeded by its name (the same indices in every run).  -> {"dir", "bytes", "files": {name: shape or "sample k of n"}}"""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    files, total, data = {}, 0, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        n = t.numel()
+        if n > DUMP_WHOLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(zlib.crc32(name.encode()))).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            files[name] = f"sample {DUMP_SAMPLE} of {n}"
+        else:
+            files[name] = list(t.shape)
+        data[name] = t.cpu().numpy()
+        total += data[name].nbytes
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    for name, a in data.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "bytes": total, "files": files}
+
+
 def _dtype_string(args):
     return "f32" if args.dtype == "f32" else BF16_DTYPE
 
@@ -537,8 +605,14 @@ def _eval_mode(args, cfg, dev):
     with torch.inference_mode():
         y = pred(x)                                            # capture (+ the replay == eager check of TapedPredictor)
         assert bool(torch.isfinite(y).all())
-        n_s, sec_s = _timed_loop(lambda: pred(x), args.t0, args.t1, args.steps, sync_each=True)
-        n_p, sec_p = _timed_loop(lambda: pred(x), 0.5, min(args.t1, 10.0), args.steps, sync_each=False)
+        last = {}
+
+        def fwd():
+            last["logits"] = pred(x)
+        n_s, sec_s = _timed_loop(fwd, args.t0, args.t1, args.steps, sync_each=True)
+        dumped = _dump_outputs(args.dump_outputs, last) if args.dump_outputs else None
+        if args.full:
+            n_p, sec_p = _timed_loop(lambda: pred(x), 0.5, min(args.t1, 10.0), args.steps, sync_each=False)
     value = B * n_s / sec_s
     gf = EVAL_GFLOP.get(args.workload)
     pub = PUBLISHED_EVAL.get(args.workload) if B == 16 else None
@@ -550,9 +624,12 @@ def _eval_mode(args, cfg, dev):
            "config": {"workload": f"{args.workload}: VeloxSeg in_ch={cfg['in_ch']} n_classes={cfg['n_classes']} patch {cfg['input_size']} windows {cfg['min_big_window_sizes']}, "
                                   f"eval forward (logits of the main head), batch {B}", "batch_per_gpu": B, "protocol": "speed_test.py:117-134: T0 warm-up, then forwards with a device synchronise "
                                   f"after each until their times sum to T1 (T0 = {args.t0} s, T1 = {args.t1} s)" + (f"; --steps {args.steps}" if args.steps > 0 else ""),
-                      "launch": "engine.TapedPredictor: the forward of this batch shape captured once, replayed as a launch tape (csrc/tape.hip)"},
-           "pipelined": {"value": round(B * n_p / sec_p, 2), "unit": "patches/s", "forwards": n_p,
-                         "note": "the same forwards enqueued back to back, ONE synchronise at the end (what a serving loop does); the headline keeps the reference's per-forward synchronise"}}
+                      "launch": "engine.TapedPredictor: the forward of this batch shape captured once, replayed as a launch tape (csrc/tape.hip)"}}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if args.full:
+        out["pipelined"] = {"value": round(B * n_p / sec_p, 2), "unit": "patches/s", "forwards": n_p,
+                            "note": "the same forwards enqueued back to back, ONE synchronise at the end (what a serving loop does); the headline keeps the reference's per-forward synchronise"}
     if gf:
         out["step_roofline"] = {"algorithmic_flops": gf * 1e9 * B, "achieved_tflops": round(gf * B / (sec_s / n_s) / 1e3, 2),
                                 "frac_fp32": round(gf * B / (sec_s / n_s) / 1e3 / FP32_PEAK_TFLOPS, 4), "note": "eval-forward flops (2 x MAC, SURVEY.md 8d) against the fp32 vector / MFMA peak"}
@@ -582,9 +659,12 @@ def _sliding_mode(args, cfg, dev):
     def one():
         logits, labels = IR.infer_volume(model, vol, (roi,) * 3, 2, overlap)
         res["dice"] = cal_dice(labels, label)
+        res["logits"], res["labels"] = logits, labels
     with torch.inference_mode():
         one()
         n, sec = _timed_loop(one, min(args.t0, 3.0), min(args.t1, 20.0), args.steps, sync_each=True)
+        dumped = _dump_outputs(args.dump_outputs, {"logits": res["logits"], "labels": res["labels"], "dice": torch.tensor([float(v) for v in res["dice"]], dtype=torch.float64)}) \
+            if args.dump_outputs else None
     gf = EVAL_GFLOP.get(args.workload)
     out = {"metric": "sliding-window inference volumes/s (4x240x240x155, overlap 0.5, sw_batch 2; arg-max + BraTS Dice included)", "value": round(n / sec, 3), "unit": "volumes/s",
            "n_gpus": 1, "steps": n, "warmup": f"{min(args.t0, 3.0)} s", "ms_per_step": round(sec / n * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -593,6 +673,8 @@ def _sliding_mode(args, cfg, dev):
                                   f"windows {cfg['min_big_window_sizes']}", "windows": len(starts), "windows_per_s": round(len(starts) * n / sec, 1),
                       "launch": "utils.inference_runtime.infer_volume: window planner on the host, vx_sw_extract / accumulate / finalize (+ fused uint8 arg-max), the window batch's forward replayed as a launch tape"},
            "dice_vs_random_labels": [round(float(v), 4) for v in res["dice"]]}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if gf:
         fl = gf * 1e9 * len(starts)
         out["step_roofline"] = {"algorithmic_flops": fl, "achieved_tflops": round(fl / (sec / n) / 1e12, 2), "frac_fp32": round(fl / (sec / n) / 1e12 / FP32_PEAK_TFLOPS, 4),

@@ -124,7 +124,7 @@ def test_bench_two_ranks_end_to_end_over_gloo():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--workload", "autopet96", "--batch", "1",
-                        "--no-cpu-baseline", "--no-eager-baseline", "--no-kernel-pass", "--dispersion-steps", "0"], capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-eager-baseline", "--no-kernel-pass", "--dispersion-steps", "0"], capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, ("exactly one JSON line from rank 0", r.stdout[-1000:])

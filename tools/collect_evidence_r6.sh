@@ -2,8 +2,8 @@
 set -x
 export TMPDIR=/tmp
 O=gpurun_out/fin6; mkdir -p $O
-NB="--no-eager-baseline --no-cpu-baseline"
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench_line.err
+NB="--full --no-eager-baseline --no-cpu-baseline"
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 timeout 300 python bench.py $NB --dtype bf16 > $O/bench_autopet128_bf16.json 2>/dev/null
 timeout 300 python bench.py $NB --workload brats128 > $O/bench_brats128_f32.json 2>/dev/null
 timeout 300 python bench.py $NB --workload brats128 --dtype bf16 > $O/bench_brats128_bf16.json 2>/dev/null
@@ -13,10 +13,10 @@ timeout 300 python bench.py $NB --workload autopet96 > $O/bench_autopet96.json 2
 timeout 300 python bench.py $NB --workload brats96 > $O/bench_brats96.json 2>/dev/null
 timeout 300 python bench.py $NB --workload hecktor > $O/bench_hecktor.json 2>/dev/null
 # the reference's published GPU protocol (speed_test.py: 10 s + 60 s) and BASELINE configs[4]
-timeout 400 python bench.py --mode eval > $O/bench_eval_autopet96_f32.json 2>/dev/null
-timeout 300 python bench.py --mode eval --dtype bf16 --t1 20 --no-cpu-baseline > $O/bench_eval_autopet96_bf16.json 2>/dev/null
-timeout 300 python bench.py --mode sliding --roi 128 > $O/bench_sliding_roi128.json 2>/dev/null
-timeout 300 python bench.py --mode sliding --roi 96 --no-cpu-baseline > $O/bench_sliding_roi96.json 2>/dev/null
+timeout 400 python bench.py --full --mode eval > $O/bench_eval_autopet96_f32.json 2>/dev/null
+timeout 300 python bench.py --full --mode eval --dtype bf16 --t1 20 --no-cpu-baseline > $O/bench_eval_autopet96_bf16.json 2>/dev/null
+timeout 300 python bench.py --full --mode sliding --roi 128 > $O/bench_sliding_roi128.json 2>/dev/null
+timeout 300 python bench.py --full --mode sliding --roi 96 --no-cpu-baseline > $O/bench_sliding_roi96.json 2>/dev/null
 # kernel summaries of the benched schedule (the JSON line of the PROFILED process is the sidecar of each CSV)
 PR="--no-eager-baseline --no-cpu-baseline --no-kernel-pass --dispersion-steps 0 --steps 100 --warmup 10"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o st --output-format csv -- python3 bench.py $PR > $O/stats.log 2>&1

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel wave-time breakdown from one rocprofv3 SQ counter pass (csv): where do the waves of each kernel spend their cycles?
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT \\
-            --output-format csv -d out -- python3 bench.py --steps 3 --warmup 2 --no-eager-baseline --no-cpu-baseline
+            --output-format csv -d out -- python3 bench.py --full --steps 3 --warmup 2 --no-eager-baseline --no-cpu-baseline
   python tools/pmc_sq.py out/*/*counter_collection.csv [name-filter ...]"""
 import csv, re, sys, collections
 path, filters = sys.argv[1], sys.argv[2:] or ["vx_"]

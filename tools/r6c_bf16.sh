@@ -1,7 +1,7 @@
 set -x
 export TMPDIR=/tmp
 O=gpurun_out/r6c; mkdir -p $O
-NB="--no-eager-baseline --no-cpu-baseline"
+NB="--full --no-eager-baseline --no-cpu-baseline"
 timeout 300 python bench.py $NB --workload brats128 > $O/brats128_f32.json 2> $O/err.log
 timeout 300 python bench.py $NB --workload brats128 --dtype bf16 > $O/brats128_bf16.json 2>> $O/err.log
 VELOXSEG_BF16_STORAGE=0 timeout 300 python bench.py $NB --workload brats128 --dtype bf16 > $O/brats128_bf16_operands_only.json 2>> $O/err.log

@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 python -m pytest tests/test_hip_ops_gpu.py -x -q -k "expand" 2>&1 | tail -2
 python -m pytest tests/test_hip_model_gpu.py tests/test_tape_gpu.py -x -q 2>&1 | tail -2
-NB="--no-eager-baseline --no-cpu-baseline --no-kernel-pass"
+NB="--full --no-eager-baseline --no-cpu-baseline --no-kernel-pass"
 for r in 1 2 3; do for x in 0 1; do
 echo wmax1=$x autopet128 $(VELOXSEG_EXPAND_WMAX1=$((x*65536)) python bench.py $NB 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['dispersion']['step_ms_p50'])")
 done; done

@@ -1,6 +1,6 @@
 export TMPDIR=/tmp
 python -m pytest tests/test_tape_gpu.py tests/test_dp_gpu.py tests/test_train_harness_gpu.py tests/test_bf16_gpu.py -x -q 2>&1 | tail -2
-NB="--no-eager-baseline --no-cpu-baseline --no-kernel-pass"
+NB="--full --no-eager-baseline --no-cpu-baseline --no-kernel-pass"
 for r in 1 2 3; do for x in 0 1; do
 echo zgdec=$x autopet128 $(VELOXSEG_ZERO_GRAD_DEC=$x python bench.py $NB 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['dispersion']['step_ms_p50'])")
 done; done
