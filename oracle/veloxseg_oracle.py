@@ -82,8 +82,15 @@ def gelu(x: Tensor) -> Tensor:
     return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
 
 
-def dropout(x: Tensor, p: float, training: bool) -> Tensor:
-    return F.dropout(x, p, training) if (training and p > 0) else x
+def dropout(x: Tensor, p: float, training: bool, masks: dict = None, key: str = None, attn: bool = False) -> Tensor:
+    """nn.Dropout.  With `masks` = dict(seed, step, sites={key: site id}) the mask is the one the HIP kernels draw for that site at that
+    {seed, step} (oracle/philox.py) instead of torch's; `key` names the site and `attn` selects the attention sites' 16-bit scheme."""
+    if not (training and p > 0):
+        return x
+    if masks is None:
+        return F.dropout(x, p, training)
+    from oracle import philox
+    return philox.apply(x, masks["seed"], masks["step"], masks["sites"][key], p, attn=attn)
 
 
 # --------------------------------------------------------------------------------------------
@@ -174,17 +181,18 @@ def relative_bias(table: Tensor, index: Tensor, l: int) -> Tensor:
 
 
 def window_attention(q: Tensor, k: Tensor, v: Tensor, bias: Tensor, M: int, p_drop: float = 0.0,
-                     training: bool = False) -> Tensor:
+                     training: bool = False, masks: dict = None, key: str = None) -> Tensor:
     """q,k: (B,h,N,M*l,cqk), v: (B,h,N,M*l,cv); same bias on every (m,m') block (PWA.py:308-327)."""
     c = q.shape[-1]
     s = torch.einsum("bhnic,bhnjc->bhnij", q, k) / (c ** 0.5)
     s = s + bias.repeat(1, M, M)[None, :, None]
     w = torch.softmax(s, -1)
-    w = dropout(w, p_drop, training)
+    w = dropout(w, p_drop, training, masks, key, attn=True)        # element index = flat index of (B, h, N, ML, ML)
     return torch.einsum("bhnij,bhnjc->bhnic", w, v)
 
 
-def pwa_attention_module(xs: List[Tensor], sd: Dict[str, Tensor], pre: str, plan: dict, drops: dict, training: bool) -> List[Tensor]:
+def pwa_attention_module(xs: List[Tensor], sd: Dict[str, Tensor], pre: str, plan: dict, drops: dict, training: bool,
+                         masks: dict = None) -> List[Tensor]:
     """MultiModal_Paired_Windows_Attention.forward (PWA.py:329-379): returns x_m + Drop(mix(scatter(attn)))."""
     M = len(xs)
     qs, ks, vs = [], [], []
@@ -201,31 +209,31 @@ def pwa_attention_module(xs: List[Tensor], sd: Dict[str, Tensor], pre: str, plan
     l = qs[0].shape[3]
     bias = relative_bias(sd[f"{pre}position_embedding.relative_position_bias_table"],
                          sd[f"{pre}position_embedding.relative_position_index"], l)
-    a = window_attention(q, k, v, bias, M, drops["attn"], training)
+    a = window_attention(q, k, v, bias, M, drops["attn"], training, masks, pre + "site_attn")
     outs = []
     for m in range(M):
         sc = scatter_windows(a[:, :, :, m * l:(m + 1) * l], plan, plan["c_v"])
         mix = F.conv3d(sc, sd[f"{pre}mix_channels.{m}.weight"], sd[f"{pre}mix_channels.{m}.bias"])
-        outs.append(xs[m] + dropout(mix, drops["proj"], training))
+        outs.append(xs[m] + dropout(mix, drops["proj"], training, masks, f"{pre}sites_proj.{m}"))
     return outs
 
 
-def ffn(x: Tensor, sd, pre: str, p: float, training: bool) -> Tensor:
-    """attention_utils.py:45-71."""
+def ffn(x: Tensor, sd, pre: str, p: float, training: bool, masks: dict = None) -> Tensor:
+    """attention_utils.py:45-71 (drop2 is drop1, :62: two draws of one module)."""
     h = gelu(F.conv3d(x, sd[pre + "linear1.weight"], sd[pre + "linear1.bias"]))
-    h = dropout(h, p, training)
+    h = dropout(h, p, training, masks, pre + "site1")
     y = F.conv3d(h, sd[pre + "linear2.weight"], sd[pre + "linear2.bias"])
-    return dropout(y, p, training)
+    return dropout(y, p, training, masks, pre + "site2")
 
 
-def pwa_block(xs: List[Tensor], sd, pre: str, plan: dict, drops: dict, training: bool) -> List[Tensor]:
+def pwa_block(xs: List[Tensor], sd, pre: str, plan: dict, drops: dict, training: bool, masks: dict = None) -> List[Tensor]:
     """Paired_Windows_TransformerBlock.forward (PWA.py:433-439): y = x + attn(x) [= 2x + mix]; z = y + FFN(LN(y))."""
-    attns = pwa_attention_module(xs, sd, pre + "attn.", plan, drops, training)
+    attns = pwa_attention_module(xs, sd, pre + "attn.", plan, drops, training, masks)
     out = []
     for m in range(len(xs)):
         y = xs[m] + attns[m]
         yn = layernorm_cf(y, sd[f"{pre}norms.{m}.weight"], sd[f"{pre}norms.{m}.bias"])
-        out.append(y + ffn(yn, sd, f"{pre}ffns.{m}.", drops["proj"], training))
+        out.append(y + ffn(yn, sd, f"{pre}ffns.{m}.", drops["proj"], training, masks))
     return out
 
 
@@ -254,7 +262,7 @@ def up_conv(x: Tensor, sd, pre: str) -> Tensor:
     return instnorm(F.conv_transpose3d(x, sd[pre + "up.weight"], sd[pre + "up.bias"], stride=2))
 
 
-def jlc(x: Tensor, sd, pre: str, groups: int, p_drop: float, training: bool) -> Tensor:
+def jlc(x: Tensor, sd, pre: str, groups: int, p_drop: float, training: bool, masks: dict = None) -> Tensor:
     """JLC.forward (conv_blocks.py:72-75)."""
     acc = x
     for i, k in enumerate((1, 3, 5)):
@@ -263,12 +271,12 @@ def jlc(x: Tensor, sd, pre: str, groups: int, p_drop: float, training: bool) -> 
         acc = acc + gelu(instnorm(F.conv3d(x, w, b, padding=k // 2, groups=groups)))
     h = gelu(F.conv3d(instnorm(acc), sd[pre + "channel_conv.1.weight"], sd[pre + "channel_conv.1.bias"]))
     y = F.conv3d(h, sd[pre + "channel_conv.3.weight"], sd[pre + "channel_conv.3.bias"])
-    return acc + dropout(y, p_drop, training)
+    return acc + dropout(y, p_drop, training, masks, pre + "site")          # the reference's channel_conv.4
 
 
-def jlc_layer(x, sd, pre, depth, groups, p_drop, training):
+def jlc_layer(x, sd, pre, depth, groups, p_drop, training, masks=None):
     for d in range(depth):
-        x = jlc(x, sd, f"{pre}{d}.", groups, p_drop, training)
+        x = jlc(x, sd, f"{pre}{d}.", groups, p_drop, training, masks)
     return x
 
 
@@ -322,7 +330,7 @@ class OracleConfig:
             grid = [g // 2 for g in grid]
 
 
-def encoder(x: Tensor, sd, cfg: OracleConfig, training: bool):
+def encoder(x: Tensor, sd, cfg: OracleConfig, training: bool, masks: dict = None):
     """Encoder.forward (model/Encoder.py:339-367) incl. Transformer_Encoder.forward (:190-204)."""
     M = cfg.M
     xs = list(torch.chunk(x, M, dim=1))                              # Encoder.py:192 (equal chunks)
@@ -330,11 +338,11 @@ def encoder(x: Tensor, sd, cfg: OracleConfig, training: bool):
     cur = []
     for m in range(M):
         w, b = sd[f"encoder.encoder_attn.patch_embeds.{m}.proj.weight"], sd[f"encoder.encoder_attn.patch_embeds.{m}.proj.bias"]
-        cur.append(dropout(F.conv3d(xs[m], w, b, stride=p), cfg.drops["proj"], training))
+        cur.append(dropout(F.conv3d(xs[m], w, b, stride=p), cfg.drops["proj"], training, masks, f"encoder.encoder_attn.sites_pos.{m}"))
     attn_feats = []
     for L in range(4):
         for d in range(cfg.depths[L]):
-            cur = pwa_block(cur, sd, f"encoder.encoder_attn.layers.{L}.blocks.{d}.", cfg.plans[L], cfg.drops, training)
+            cur = pwa_block(cur, sd, f"encoder.encoder_attn.layers.{L}.blocks.{d}.", cfg.plans[L], cfg.drops, training, masks)
         attn_feats.append(cur)
         if L < 3:
             cur = [patch_merging(cur[m], sd, f"encoder.encoder_attn.layers.{L}.downs.{m}.") for m in range(M)]
@@ -344,23 +352,27 @@ def encoder(x: Tensor, sd, cfg: OracleConfig, training: bool):
         a = instnorm(F.conv3d(torch.cat(attn_feats[L], 1), sd[f"encoder.attn2conv_{L + 1}.0.weight"],
                               sd[f"encoder.attn2conv_{L + 1}.0.bias"]))
         y = down_conv(prev, sd, f"encoder.encoder_conv.down{L + 1}.", p if L == 0 else 2) + a
-        prev = jlc_layer(y, sd, f"encoder.encoder_conv.layer{L + 1}.", cfg.conv_depths[L], cfg.groups[L], cfg.drops["conv"], training)
+        prev = jlc_layer(y, sd, f"encoder.encoder_conv.layer{L + 1}.", cfg.conv_depths[L], cfg.groups[L], cfg.drops["conv"], training, masks)
         encs.append(prev)
     return attn_feats, encs
 
 
-def decoder_trunk(e: List[Tensor], sd, pre: str, cfg: OracleConfig, training: bool):
+def decoder_trunk(e: List[Tensor], sd, pre: str, cfg: OracleConfig, training: bool, masks: dict = None):
     """Shared trunk of Seg_Decoder / RC_Decoder (model/Decoder.py:160-164, 85-88)."""
-    up3 = jlc_layer(e[2] + up_conv(e[3], sd, pre + "layer_up3."), sd, pre + "layer3.", cfg.conv_depths[2], cfg.groups[2], cfg.drops["conv"], training)
-    up2 = jlc_layer(e[1] + up_conv(up3, sd, pre + "layer_up2."), sd, pre + "layer2.", cfg.conv_depths[1], cfg.groups[1], cfg.drops["conv"], training)
-    up1 = jlc_layer(e[0] + up_conv(up2, sd, pre + "layer_up1."), sd, pre + "layer1.", cfg.conv_depths[0], cfg.groups[0], cfg.drops["conv"], training)
+    cd = cfg.drops["conv"]
+    up3 = jlc_layer(e[2] + up_conv(e[3], sd, pre + "layer_up3."), sd, pre + "layer3.", cfg.conv_depths[2], cfg.groups[2], cd, training, masks)
+    up2 = jlc_layer(e[1] + up_conv(up3, sd, pre + "layer_up2."), sd, pre + "layer2.", cfg.conv_depths[1], cfg.groups[1], cd, training, masks)
+    up1 = jlc_layer(e[0] + up_conv(up2, sd, pre + "layer_up1."), sd, pre + "layer1.", cfg.conv_depths[0], cfg.groups[0], cd, training, masks)
     return up1, up2, up3
 
 
-def forward(x: Tensor, sd: Dict[str, Tensor], cfg: OracleConfig, training: bool):
-    """VeloxSeg.forward (model/VeloxSeg.py:186-226).  Train -> list; eval -> logits."""
-    attn_feats, encs = encoder(x, sd, cfg, training)
-    up1, up2, up3 = decoder_trunk(encs, sd, "decoder.", cfg, training)
+def forward(x: Tensor, sd: Dict[str, Tensor], cfg: OracleConfig, training: bool, masks: dict = None):
+    """VeloxSeg.forward (model/VeloxSeg.py:186-226).  Train -> list; eval -> logits.
+    masks: None (torch's dropout) or dict(seed=, step=, sites={key: site id}); every dropout site then applies the mask the HIP kernels
+    draw for that {seed, step}.  Keys: "<module path>.<attribute>[.<modality>]" of the site in veloxseg_amd's model (encoder.encoder_attn.
+    sites_pos.m, <block>.attn.site_attn, <block>.attn.sites_proj.m, <block>.ffns.m.site1 / site2, <JLC block>.site); the ids come from the caller."""
+    attn_feats, encs = encoder(x, sd, cfg, training, masks)
+    up1, up2, up3 = decoder_trunk(encs, sd, "decoder.", cfg, training, masks)
     s = cfg.patch_size
     main = pixel_shuffle3d(F.conv3d(up1, sd["decoder.out_conv1.0.weight"], sd["decoder.out_conv1.0.bias"], padding=1), s)
     if not training:
@@ -378,7 +390,7 @@ def forward(x: Tensor, sd: Dict[str, Tensor], cfg: OracleConfig, training: bool)
         for L in range(4):
             cat = torch.cat([attn_feats[L][m], encs[L]], 1)
             e.append(instnorm(F.conv3d(cat, sd[f"{pre}enc2rc_{L + 1}.0.weight"], sd[f"{pre}enc2rc_{L + 1}.0.bias"])))
-        r1, _, _ = decoder_trunk(e, sd, pre, cfg, training)
+        r1, _, _ = decoder_trunk(e, sd, pre, cfg, training, masks)
         rcs.append(pixel_shuffle3d(F.conv3d(r1, sd[pre + "out_conv.0.weight"], sd[pre + "out_conv.0.bias"], padding=1), s))
         grams.append(gram(r1))
     return preds + [torch.cat(rcs, 1)] + [gram(up1)] + grams

@@ -14,6 +14,8 @@ Fixtures (all fp32, CPU, torch.manual_seed-ed; see CASES below):
                    grads_sample{param->tensor for a few small params})
   ops.pt    : per-op micro goldens (LayerNorm, gather/scatter, attention w/ bias M=2, PatchMerging,
               JLC, DownConv, UpConv, PixelShuffle, Gram, DiceLoss/CE, full Loss)
+  <case>.pt of DROP_CASES : one training step with dropout ON (masks of oracle/philox.py for the stored seed /
+              step / site ids): train_outputs, loss, grad_norms, grads_small
 Usage: python tests/golden/make_golden.py [case ...]      (no argument = every case + ops.pt)
 """
 import os
@@ -103,7 +105,8 @@ def install_stub():
 
 
 sys.path.insert(0, HERE)
-from recipe import BIG_CASES, CASES, LOSS_CFG, fill_state_dict, make_inputs, tensor_sha, sd_sha, compact, pack_mask  # noqa: E402
+from recipe import BIG_CASES, CASES, DROP_CASES, DROP_SEED, DROP_STEP, LOSS_CFG, dropout_sites, fill_state_dict, make_inputs, tensor_sha, sd_sha, compact, pack_mask  # noqa: E402,E501
+ROOT = os.path.dirname(os.path.dirname(HERE))
 
 
 def make_case(name, cfg, B):
@@ -144,6 +147,98 @@ def make_case(name, cfg, B):
     torch.save(fix, os.path.join(HERE, name + ".pt"))
     print(name, "params", sum(p.numel() for p in model.parameters()), "loss", float(loss),
           "size MB", os.path.getsize(os.path.join(HERE, name + ".pt")) / 1e6)
+
+
+class _RestatedDropout(torch.nn.Module):
+    """Stands in for one nn.Dropout of the reference while a dropout-on fixture is generated: multiplies by the mask the HIP kernels draw
+    (oracle/philox.py) for the project site its n-th call corresponds to (`keys`, in call order)."""
+
+    def __init__(self, p, keys, sites, attn):
+        super().__init__()
+        self.p, self.keys, self.sites, self.attn, self.calls = float(p), list(keys), sites, attn, 0
+
+    def forward(self, x):
+        if not self.training or self.p == 0:
+            return x
+        from oracle import philox
+        key = self.keys[self.calls]
+        self.calls += 1
+        return philox.apply(x, DROP_SEED, DROP_STEP, self.sites[key], self.p, attn=self.attn)
+
+
+def _restate_dropouts(model, sites, M):
+    """replace every nn.Dropout the reference model holds; returns the stand-ins.  Reference module -> project site (by module path; the
+    state-dict keys of the two models are identical):
+      encoder.encoder_attn.pos_drop        called once per modality (Encoder.py:196)  -> encoder.encoder_attn.sites_pos.<m>
+      <block>.attn.dropout_weight          (b, head, Ns, ml, ml) weights (PWA.py:323) -> <block>.attn.site_attn (16-bit scheme)
+      <block>.attn.dropout_attns.<m>                                                    -> <block>.attn.sites_proj.<m>
+      <block>.ffns.<m>.drop1               drop2 is drop1 (attention_utils.py:62)     -> .site1 (first call), .site2 (second)
+      <JLC block>.channel_conv.4           (conv_blocks.py:69)                        -> <JLC block>.site"""
+    import re
+    subs = []
+    for name, mod in list(model.named_modules()):
+        if not isinstance(mod, torch.nn.Dropout):
+            continue
+        attn = False
+        if name.endswith(".pos_drop"):
+            keys = [f"{name[:-len('.pos_drop')]}.sites_pos.{m}" for m in range(M)]
+        elif name.endswith(".dropout_weight"):
+            keys, attn = [name[:-len(".dropout_weight")] + ".site_attn"], True
+        elif re.search(r"\.dropout_attns\.\d+$", name):
+            base, m = name.rsplit(".dropout_attns.", 1)
+            keys = [f"{base}.sites_proj.{m}"]
+        elif name.endswith(".drop1"):
+            base = name[:-len(".drop1")]
+            keys = [base + ".site1", base + ".site2"]
+        elif name.endswith(".channel_conv.4"):
+            keys = [name[:-len(".channel_conv.4")] + ".site"]
+        else:
+            raise RuntimeError(f"reference dropout {name} has no project site")
+        new = _RestatedDropout(mod.p, keys, sites, attn)
+        parent = model.get_submodule(name.rsplit(".", 1)[0])
+        for a, child in list(parent._modules.items()):
+            if child is mod:                 # (FFN: drop1 and drop2 are one module)
+                parent._modules[a] = new
+        subs.append(new)
+    return subs
+
+
+def make_drop_case(name, cfg, B):
+    """a training step of the reference with every dropout at its configured rate, masks restated from the HIP kernels' generator"""
+    sys.path.append(ROOT)
+    from model.VeloxSeg import VeloxSeg
+    from utils.loss import Loss
+    from veloxseg_amd.model.VeloxSeg import VeloxSeg as ProjectVeloxSeg
+    sites = dropout_sites(ProjectVeloxSeg(**cfg))
+    torch.manual_seed(12345)
+    model = VeloxSeg(**cfg)
+    sd = fill_state_dict(model.state_dict(), seed=7)
+    model.load_state_dict(sd)
+    M = len(cfg["in_ch"])
+    subs = _restate_dropouts(model, sites, M)
+    x, labels = make_inputs(cfg, B)
+    model.train()
+
+    def _contig_grad(mod, inp, out):         # (the CPU autograd work-around of make_case)
+        if out.requires_grad:
+            out.register_hook(lambda g: g.contiguous())
+    for dec in [model.decoder] + list(model.rc_decoders):
+        dec.layer1.register_forward_hook(_contig_grad)
+    outs = model(x)
+    used = sorted(k for s in subs for k in s.keys[:s.calls])
+    assert all(s.calls == len(s.keys) for s in subs), [(s.keys, s.calls) for s in subs if s.calls != len(s.keys)]
+    assert used == sorted(sites), (set(sites) ^ set(used))
+    args = types.SimpleNamespace(model_name="VeloxSeg")
+    crit = Loss(args, LOSS_CFG, torch.device("cpu"), num_modal=M)
+    loss = crit(outs, labels, sr_labels=x)
+    loss.backward()
+    grad_norms = {n: float(p.grad.double().norm()) for n, p in model.named_parameters()}
+    small = {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.numel() <= 600}
+    fix = dict(config=cfg, batch=B, seed=DROP_SEED, step=DROP_STEP, sites=sites, sd_seed=7, sd_sha256=sd_sha(sd),
+               x_sha256=tensor_sha(x), labels_sha256=tensor_sha(labels), train_outputs=[compact(o) for o in outs], loss=float(loss.detach()),
+               loss_cfg=LOSS_CFG, grad_norms=grad_norms, grads_small=small)
+    torch.save(fix, os.path.join(HERE, name + ".pt"))
+    print(name, "sites", len(sites), "loss", float(loss), "size MB", os.path.getsize(os.path.join(HERE, name + ".pt")) / 1e6)
 
 
 def make_ops():
@@ -280,3 +375,6 @@ if __name__ == "__main__":
     for name, (cfg, B) in CASES.items():
         if not only or name in only:
             make_case(name, cfg, B)
+    for name, (cfg, B) in DROP_CASES.items():
+        if not only or name in only:
+            make_drop_case(name, cfg, B)

@@ -142,3 +142,27 @@ CASES = {
 }
 BIG_CASES = ("g5_128_m2", "g6_128_brats", "g7_96_m2")      # fixtures store the arg-max mask bit-packed and coarser subsamples
 LOSS_CFG = {"deep_Loss_weight": [1, 1, 1, 1], "RC_Loss_weight": 0.5, "Feature_Loss_weight": 2.0}
+
+# Dropout-on cases (kept apart from CASES so that no existing parametrisation changes): the configured rate 0.1 at every site, B = 2, and the
+# {seed, step} pair the masks are drawn for (seed >= 2^32, step > 0: both halves of the 64-bit key and the step term are exercised).
+DROP_SEED, DROP_STEP = 0x1_2345_6789, 3
+DROP_CASES = {
+    "g1_48_m2_drop": (dict(CASES["g1_48_m2"][0], proj_drop=0.1, conv_drop=0.1, attn_drop=0.1), 2),
+}
+
+
+def dropout_sites(model) -> dict:
+    """oracle dropout key -> site id of a veloxseg_amd model: "<module path>.<attribute>" for the scalar sites (site_attn, site1, site2,
+    site) and "<module path>.<attribute>.<modality>" for the per-modality lists (sites_pos, sites_proj); oracle.veloxseg_oracle.forward(masks=)
+    names its sites the same way"""
+    out = {}
+    for name, mod in model.named_modules():
+        pre = name + "." if name else ""
+        for a in ("site_attn", "site1", "site2", "site"):
+            v = getattr(mod, a, None)
+            if isinstance(v, int):
+                out[pre + a] = v
+        for a in ("sites_pos", "sites_proj"):
+            for i, v in enumerate(getattr(mod, a, None) or []):
+                out[f"{pre}{a}.{i}"] = int(v)
+    return out

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import veloxseg_oracle as O
-from recipe import CASES, LOSS_CFG, check_compact, fill_state_dict, make_inputs, sd_sha, tensor_sha, unpack_mask
+from recipe import CASES, DROP_CASES, DROP_SEED, DROP_STEP, LOSS_CFG, check_compact, dropout_sites, fill_state_dict, make_inputs, sd_sha, tensor_sha, unpack_mask
 
 ATOL, RTOL = 2e-4, 2e-4
 
@@ -141,3 +141,47 @@ def test_upsample_matches_aten():
     y = O.upsample_trilinear(x, [16, 24, 12])
     r = torch.nn.functional.interpolate(x, size=[16, 24, 12], mode="trilinear", align_corners=True)
     torch.testing.assert_close(y, r, atol=2e-6, rtol=1e-5)
+
+
+@pytest.mark.parametrize("name", list(DROP_CASES))
+def test_train_dropout_masks_vs_reference(golden_dir, name):
+    """Dropout ON at every site (p = 0.1): the oracle, applying the masks of oracle/philox.py through forward(masks=), against the reference's
+    own training step with each of its nn.Dropout modules replaced by the same restated masks (make_golden.make_drop_case).  Same bars as
+    test_train_outputs_loss_grads.  This pins WHERE the oracle drops (after which op, before which residual add, which tensor index) to the
+    reference's placement, so that the HIP path, compared with the oracle in tests/test_dropout_parity_gpu.py, cannot share a placement error
+    with it.  The site ids are the ones veloxseg_amd's model assigns (built here on the CPU: construction needs no GPU)."""
+    from veloxseg_amd.model.VeloxSeg import VeloxSeg
+    fix = load(golden_dir, name + ".pt")
+    cfg_d, B = DROP_CASES[name]
+    assert fix["config"] == cfg_d and fix["batch"] == B
+    cfg = O.OracleConfig(**cfg_d)
+    sd = fill_state_dict(O.state_dict_template(cfg), seed=fix["sd_seed"])
+    assert sd_sha(sd) == fix["sd_sha256"], "state-dict recipe drifted (RNG?)"
+    x, labels = make_inputs(cfg_d, B)
+    assert tensor_sha(x) == fix["x_sha256"] and tensor_sha(labels) == fix["labels_sha256"]
+    sites = dropout_sites(VeloxSeg(**cfg_d))
+    assert sites == fix["sites"], "the model's dropout site ids changed: regenerate the fixture (make_golden.py " + name + ")"
+    assert (fix["seed"], fix["step"]) == (DROP_SEED, DROP_STEP)
+    params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if torch.is_floating_point(v)}
+    full = dict(sd)
+    full.update(params)
+    masks = dict(seed=fix["seed"], step=fix["step"], sites=sites)
+    outs = O.forward(x, full, cfg, training=True, masks=masks)
+    assert len(outs) == len(fix["train_outputs"]) == 4 + 1 + 1 + cfg.M
+    for i, (o, r) in enumerate(zip(outs, fix["train_outputs"])):
+        check_compact(o, r, ATOL, RTOL, f"train output {i}")
+    L = O.loss(outs, labels, x, cfg.M, LOSS_CFG)
+    assert abs(float(L) - fix["loss"]) <= 1e-4 * abs(fix["loss"])
+    L.backward()
+    bad = []
+    for k, p in params.items():
+        gn = float(p.grad.double().norm())
+        ref = fix["grad_norms"][k]
+        if abs(gn - ref) > 2e-3 * max(ref, 1e-3):
+            bad.append((k, gn, ref))
+    assert not bad, bad[:5]
+    for k, g in fix["grads_small"].items():
+        torch.testing.assert_close(params[k].grad, g, atol=5e-4, rtol=5e-3, msg=lambda m: f"{k}: {m}")
+    # and the masks matter at this bar: the same step with different masks (another step number) is far from the fixture
+    o2 = O.forward(x, sd, cfg, training=True, masks=dict(masks, step=fix["step"] + 1))
+    assert abs(float(O.loss(o2, labels, x, cfg.M, LOSS_CFG)) - fix["loss"]) > 1e-3 * abs(fix["loss"])

@@ -315,3 +315,43 @@ def test_pipelined_decoder_tail_trains_like_the_joined_step():
     # walk by +-lr per step in either run; the two runs must agree in norm)
     rel = float((res[False][1] - res[True][1]).norm() / res[False][1].norm())
     assert rel < 2e-3, rel
+
+
+def test_pipelined_decoder_tail_with_dropout_tracks_the_joined_step():
+    """The same A/B as test_pipelined_decoder_tail_trains_like_the_joined_step at the configured dropout rates (0.1 at every site): the pipelined tail
+    bumps the {seed, step} word in place at the head of step N + 1 while the decoder tail of step N may still run, so a tail that re-reads the step
+    word would draw the next step's masks.  Losses of 5 consecutive steps and the parameters after them agree with the joined step at the same bars,
+    and both runs leave the step word at start + 5."""
+    import types
+    from bench import LOSS_CFG, WORKLOADS, synth
+    from veloxseg_amd.engine import TrainEngine
+    from veloxseg_amd.model.VeloxSeg import VeloxSeg
+    from veloxseg_amd.utils.loss import Loss
+    import veloxseg_amd.functional as VF
+    cfg, _ = WORKLOADS["autopet96"]
+    cfg = dict(cfg, proj_drop=0.1, conv_drop=0.1, attn_drop=0.1)
+    B = 2
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = {}
+    for pipe in (False, True):
+        VF.reset_dropout_sites()
+        torch.manual_seed(3)
+        model = VeloxSeg(**cfg).cuda()
+        crit = Loss(types.SimpleNamespace(model_name="VeloxSeg"), LOSS_CFG, None, num_modal=len(cfg["in_ch"]))
+        eng = TrainEngine(model, crit, (B, sum(cfg["in_ch"]), *cfg["input_size"]), lr=1e-3, use_graph=True, overlap=False, pipeline_tail=pipe)
+        VF.rng_state(dev).copy_(torch.tensor([0x3_0000_0005, 10], dtype=torch.int64))
+        losses = []
+        for i in range(5):
+            x, lab = synth(cfg, B, "cuda", 100 + i)
+            losses.append(eng.step(x, lab).clone())
+        assert eng.use_graph and eng.graphs is not None
+        assert eng._tail_pending == pipe
+        eng.flush()
+        p_now = eng.flat.param.clone()
+        torch.cuda.synchronize()
+        assert [int(v) for v in VF.rng_state(dev).cpu()] == [0x3_0000_0005, 15]
+        res[pipe] = ([float(l) for l in losses], p_now.cpu())
+    for a, b in zip(res[False][0], res[True][0]):
+        assert abs(a - b) <= 2e-4 * abs(a), res
+    rel = float((res[False][1] - res[True][1]).norm() / res[False][1].norm())
+    assert rel < 2e-3, rel

@@ -1198,6 +1198,8 @@ class TrainEngine:
             self._tail_pending = False
         self._fan(G["dec_fwd"], 0)
         G["loss"].replay()
+        if getattr(self, "_last_parts", None) is not None:
+            self._last_outputs = None          # the replay rewrote the parts: last_outputs assembles them again instead of returning an earlier step's concatenation
         split, n = self.flat.split, self.flat.numel
         wg_lane = None
         if "dec_wg" in G and self.replay_mode == "tape" and WG_EARLY and len(G["dec_bwd"]) <= 3:
