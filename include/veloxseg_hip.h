@@ -249,8 +249,8 @@ int vx_jlc_cl_bwd(const float* g1, const float* g3, const float* g5, const float
  * entry; a null dw skips that tensor's store); W <= 32, W % 4 == 0, H % 4 == 0, group width 4 / 8 / 16.  Bias gradients are not computed (zero behind an InstanceNorm). */
 int vx_jlc_wgrad_tz_ok(int C, int G, int D, int H, int W);
 int vx_jlc_wgrad_tz_set_min_voxels(long v);
-int vx_jlc_wgrad_tz_set_blocks(int n);     /* blocks per launch; 0 (default): 128 with producer / consumer waves -- half the chip: the step is fastest there -- 256 for the one-role kernel (VELOXSEG_WG_TZ_BLOCKS) */
-int vx_jlc_wgrad_tz_set_spec(int on);      /* 1 (default; VELOXSEG_WG_SPEC): 512-thread blocks, waves 4..7 stage step dx + 1 while waves 0..3 run the MFMAs of step dx; 0: the one-role kernel (A/B, tests) */
+int vx_jlc_wgrad_tz_set_blocks(int n);     /* blocks per launch; 0 (default): 128 with producer / consumer waves -- half the chip: the step is fastest there -- 256 for the one-role kernel */
+int vx_jlc_wgrad_tz_set_spec(int on);      /* 1 (default): 512-thread blocks, waves 4..7 stage step dx + 1 while waves 0..3 run the MFMAs of step dx; 0: the one-role kernel (A/B, tests) */
 int vx_jlc_wgrad_tz_set_f16(int on);     /* with vx_jlc_tz_set_pieces(22): 1 = the weight gradients on two scaled fp16 pieces as well (A/B; default 0 = three bf16 pieces) */
 int vx_jlc_wgrad_tz(const float* x, const float* g1, const float* g3, const float* g5, float* dw1, float* dw3, float* dw5, int B, int C, int G, int D, int H, int W,
                     void* stream);
@@ -337,7 +337,7 @@ int vx_patchify_bs_h(const float* x, long batch_stride, void* out, int B, int C,
 /* (round 6) the patch embedding itself (kernel == stride == 4, no padding; Encoder.py:150-156, MONAI PatchEmbed "conv") WITHOUT a patchified copy: the
  * product and its weight gradient gather the 4 x 4 x 4 patches from x by address.  Do, Ho, Wo: the OUTPUT grid (x is Cin x 4Do x 4Ho x 4Wo per sample,
  * batch_stride floats apart); Cout % 16 == 0, Wo % 4 == 0, Cin <= 8.  The forward sums in the order of vx_patchify + vx_pw_conv_fwd (bit-identical).
- * vx_patch_embed_ok: 1 where the dispatcher takes these kernels (VELOXSEG_PATCH_FUSED=0: never) */
+ * vx_patch_embed_ok: 1 where the dispatcher takes these kernels */
 int vx_patch_embed_ok(int Cin, int Cout, int Do, int Ho, int Wo, int K);
 int vx_patch_embed_fwd(const float* x, long batch_stride, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Do, int Ho, int Wo, void* stream);
 int vx_patch_embed_bwd_weight(const float* x, long batch_stride, const float* dy, float* dw, float* db, int B, int Cin, int Cout, int Do, int Ho, int Wo, void* stream);
@@ -437,9 +437,9 @@ int vx_pwa_attn_set_mfma(int on);
  * kernels run).  vx_pwa_attn_set_f16_bwd(0): A/B knob, those geometries back on the fp32 kernels; default 1 (selected when bit 1 of vx_pwa_attn_set_mfma is set). */
 int vx_pwa_attn_bwd1h_ok(const VxPwaPlan* plan, int B, int M, int cq, int cv);
 int vx_pwa_attn_set_f16_bwd(int on);
-int vx_pwa_attn_set_f16_bwd_ragged(int on);   /* A/B (round 6): window lengths that are not multiples of 64 (27 / 216 / 32 tokens: the shipped 96^3 and Hecktor geometries) on the f16-pipe backward too -- padded 64-token chunks: 0 off, 1 (default, VELOXSEG_F16_BWD_RAGGED) where a window fills >= 3/4 of its chunks (216 tokens), 2 every ragged length (tests) */
-int vx_pwa_attn_set_f16_bwd_m1(int on);       /* A/B (round 6): windows of ONE modality (BraTS) on the f16-pipe backward (MF = 1 instance): 0 (default, VELOXSEG_F16_BWD_M1: measured no gain at BraTS' batch of 2), 1 on, 2 on for >= 512 tokens */
-int vx_pwa_attn_set_short(int on);       /* 1 (default; VELOXSEG_B1_SHORT): single-modality windows below 512 tokens take the one-pass MFMA backward although l % 16 == 0 (BraTS: 2 x faster than the VALU kernels there); 0: the selection of rounds 3 - 5 (A/B, tests) */
+int vx_pwa_attn_set_f16_bwd_ragged(int on);   /* A/B (round 6): window lengths that are not multiples of 64 (27 / 216 / 32 tokens: the shipped 96^3 and Hecktor geometries) on the f16-pipe backward too -- padded 64-token chunks: 0 off, 1 (default) where a window fills >= 3/4 of its chunks (216 tokens), 2 every ragged length (tests) */
+int vx_pwa_attn_set_f16_bwd_m1(int on);       /* A/B (round 6): windows of ONE modality (BraTS) on the f16-pipe backward (MF = 1 instance): 0 (default: measured no gain at BraTS' batch of 2), 1 on, 2 on for >= 512 tokens */
+int vx_pwa_attn_set_short(int on);       /* 1 (default): single-modality windows below 512 tokens take the one-pass MFMA backward although l % 16 == 0 (BraTS: 2 x faster than the VALU kernels there); 0: the selection of rounds 3 - 5 (A/B, tests) */
 
 /* ---------------------------------------------------------------------------------------------
  * Loss side (utils/loss.py:30-66, common_function.py:8-14, VeloxSeg.py:177-184)
@@ -472,7 +472,7 @@ int vx_seg_loss_bwd4(const float* lg0, const float* lg1, const float* lg2, const
  * vx_seg_loss_bwd4.  Backward: dl0 full resolution, dl1..dl3 on the heads' grids (the adjoint of the interpolation runs inside the kernels);
  * ws = vx_seg_loss_ds_ws_floats(...) floats of workspace.  vx_seg_loss_ds_ok: 1 when the shape is covered (C in 2..4, W % 4 == 0, W/4 divides 64). */
 int vx_seg_loss_ds_ok(int C, int D, int H, int W);
-int vx_seg_loss_ds_set_columns(int on);      /* 1 (default; VELOXSEG_DS_COLUMNS): the column-owner kernels; 0: the row-sweep kernels (A/B, tests) */
+int vx_seg_loss_ds_set_columns(int on);      /* 1 (default): the column-owner kernels; 0: the row-sweep kernels (A/B, tests) */
 int vx_seg_loss_ds_ws_floats(const int* low_dims, int nh, int B, int C, int D);
 int vx_seg_loss_ds_fwd(const float* l0, const float* l1, const float* l2, const float* l3, const int* low_dims, int nh, const void* labels, int lab_kind,
                        double* acc, int B, int C, int D, int H, int W, void* stream);
@@ -497,7 +497,7 @@ int vx_upsample_trilinear_fwd(const float* x, float* out, long BC, int d, int h,
 int vx_upsample_trilinear_bwd(const float* dout, float* dx, float* ws, long BC, int d, int h, int w, int D, int H, int W, void* stream);
 
 /* ConvTranspose3d(k=2, s=2) specialised (conv_blocks.py:29-35): w = (Ci, Co, 2,2,2); x: (B,Ci,d,h,w); y: (B,Co,2d,2h,2w) */
-int vx_upconv_set_mfma4(int on);      /* 1 (default; VELOXSEG_UPCONV_MFMA4): 16 x 64 MFMA tiles with 16-byte accesses on the coarse levels when the row length is a multiple of 4; 0: the 16 x 16 tiles (A/B, tests) */
+int vx_upconv_set_mfma4(int on);      /* 1 (default): 16 x 64 MFMA tiles with 16-byte accesses on the coarse levels when the row length is a multiple of 4; 0: the 16 x 16 tiles (A/B, tests) */
 int vx_upconv_k2s2_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int Co, int d, int h, int wd, void* stream);
 int vx_upconv_k2s2_bwd_data(const float* dy, const float* w, float* dx, int B, int Ci, int Co, int d, int h, int wd, void* stream);
 /* weight gradient of the same layer as one MFMA GEMM (M = Ci, N = Co * 8 taps, K = B * d * h * wd): dw (Ci, Co, 2, 2, 2) +=.  Ci, Co multiples of 16, Ci <= 128 */
@@ -537,7 +537,7 @@ int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float co
  * vx_conv_mfma_ws_floats(Cin, Cout, K, backward) floats for the operand-order weight image (written by every call).  bwd_data: accumulate = 1 adds
  * into dx.  vx_conv_mfma_ok: 1 when the shape is covered (D, H, W multiples of the stride, Cout % 4 == 0). */
 int vx_conv_mfma_ok(int Cin, int Cout, int D, int H, int W, int K, int S, int P, int G, int ps);
-int vx_conv_mfma_set_stem_f16(int on);   /* opt-in (default 0, or VELOXSEG_STEM_F16): the stem (k = 7, s = 4, p = 3, 16 output channels, W % 64 == 0, H % 16 == 0; 1: <= 2 input channels, 2: also 4) as a Toeplitz GEMM on the f16 pipe with LDS-staged input rows */
+int vx_conv_mfma_set_stem_f16(int on);   /* on by default (1; 0: the fp32 gather kernel): the stem (k = 7, s = 4, p = 3, 16 output channels, W % 64 == 0, H % 16 == 0; 1: <= 2 input channels, 2: also 4) as a Toeplitz GEMM on the f16 pipe with LDS-staged input rows */
 int vx_conv_mfma_set_stem_pieces(int np);      /* 2 (default, the fp32 mode): fp32-accurate products from two scaled fp16 pieces; 1 (the bf16 mode): plain fp16 operands, one MFMA per step, half the LDS -- also selects the f16-pipe stem for 4 input channels */
 int vx_conv_mfma_stem_pieces(void);
 int vx_conv_mfma_ws_floats(int Cin, int Cout, int K, int backward);

@@ -137,3 +137,27 @@ def test_cpp_operator_module_builds_and_loads():
         assert hasattr(m, name), name
     with pytest.raises(RuntimeError, match="no CPU"):
         VF.conv3d(torch.zeros(1, 4, 4, 4, 4), torch.zeros(4, 4, 1, 1, 1))
+
+
+def test_supported_environment_variables():
+    """no kernel variant is an environment switch: the VELOXSEG_* names the sources read are exactly the supported list of INTEGRATION.md, and the native library
+    reads its environment in csrc/tape.hip only (variants are C-ABI setters, module attributes and constructor arguments)"""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = [os.path.join(root, "__graft_entry__.py")]
+    for top in ("veloxseg_amd", "include"):
+        for d, _, names in os.walk(os.path.join(root, top)):
+            files += [os.path.join(d, n) for n in names if n.endswith((".py", ".cpp", ".hip", ".h", ".c"))]
+    read = lambda p: open(p, encoding="utf-8", errors="replace").read()
+    found = {}
+    for p in files:
+        for name in re.findall(r"VELOXSEG_[A-Z0-9_]+", read(p)):
+            found.setdefault(name, os.path.relpath(p, root))
+    found.pop("VELOXSEG_HIP_H", None)                # the header's include guard
+    doc = read(os.path.join(root, "INTEGRATION.md"))
+    section = doc.split("### Environment variables (`VELOXSEG_*`)", 1)[1].split("\n### ", 1)[0]
+    table = set(re.findall(r"^\| `(VELOXSEG_[A-Z0-9_]+)` \|", section, flags=re.M))
+    assert table and len(table) <= 20, sorted(table)
+    assert set(found) == table, {"read but not in INTEGRATION.md's table": {n: found[n] for n in set(found) - table}, "in the table but read nowhere": sorted(table - set(found))}
+    csrc = os.path.join(root, "veloxseg_amd", "csrc")
+    assert sorted(n for n in os.listdir(csrc) if "getenv(" in read(os.path.join(csrc, n))) == ["tape.hip"]

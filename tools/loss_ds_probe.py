@@ -20,4 +20,4 @@ for it in range(8):
     torch.cuda.synchronize()
     if it >= 3:
         tf += e[0].elapsed_time(e[1]); tb += e[1].elapsed_time(e[2])
-print(f"dbg={os.environ.get('VX_DS_DBG', '0')}: fwd {tf / 5 * 1e3:.1f} us  bwd {tb / 5 * 1e3:.1f} us")
+print(f"fwd {tf / 5 * 1e3:.1f} us  bwd {tb / 5 * 1e3:.1f} us")

@@ -15,8 +15,7 @@ cfg, B = WORKLOADS[wl]
 if len(sys.argv) > 2:
     B = int(sys.argv[2])
 n = int(sys.argv[3]) if len(sys.argv) > 3 else 300
-# A/B: VX_SOAK_OFF=f16bwd,cl,v4 switches the named kernel families back to their predecessors (to find the source of run-to-run deviations); VELOXSEG_STEM_F16=1 turns the
-# opt-in stem kernel on
+# A/B: VX_SOAK_OFF=f16bwd,cl,v4 switches the named kernel families back to their predecessors (to find the source of run-to-run deviations)
 from veloxseg_amd import _hip as H
 H.LIB.load()
 for name in filter(None, os.environ.get("VX_SOAK_OFF", "").split(",")):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The grouped weight-gradient launch that closes the encoder backward of autopet128 B = 4 (job list printed by VX_WGG_DBG=1), alone on the GPU: the whole launch and its parts."""
+"""The grouped weight-gradient launch that closes the encoder backward of autopet128 B = 4 (job list as the library's debug print of round 6 listed it), alone on the GPU: the whole launch and its parts."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch

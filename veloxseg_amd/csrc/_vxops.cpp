@@ -34,7 +34,7 @@ typedef c10::optional<Tensor> OptT;
 namespace {
 
 struct Flags {
-    bool fuse_blocks = true, use_s1 = true, use_conv_mfma = true, bf16_expand = false, use_expand_mfma = true, use_gconv1 = true, use_wgrad_ws = false, use_patchify = true, use_in_row = true, fuse_gelu = true, fuse_pw_bwd = true, use_down_mfma = true, skip_in_bias = true, in_split2 = true, fuse_res = true, fuse_bwd_add = true;
+    bool fuse_blocks = true, use_s1 = true, use_conv_mfma = true, bf16_expand = false, use_expand_mfma = true, use_gconv1 = true, use_wgrad_ws = false, use_patchify = true, use_in_row = true, skip_in_bias = true, in_split2 = true, fuse_res = true, fuse_bwd_add = true;
     int64_t pw_mfma_max_v = 4096, in_row_max = 4096;
     int tile_min_c = 32;              // JLC channel stage on the tile-GEMM kernels (pwa_fused.hip vx_inmlp_*) from this many channels up, mlp.hip below (functional.TILE_MIN_C)
     bool upconv_wgrad_mfma = true;    // (A/B) ConvTranspose weight gradient as one MFMA GEMM (pointwise.hip vx_upconv_k2s2_wgrad) vs the generic strided-conv kernel
@@ -107,24 +107,19 @@ inline float* grad_ptr(const Tensor& p) {          // running gradient buffer of
     return p.grad().data_ptr<float>();
 }
 
-// ------------------------------------------------------------------------------------------------------------------- weight-gradient side stream
+// ------------------------------------------------------------------------------------------------------------------- deferred weight gradients
 // In the backward pass only the INPUT gradient of a convolution is on the critical path (the previous layer waits for it); its weight gradient
-// is needed by the optimizer alone.  When enabled (TrainEngine turns it on around loss.backward() and joins before the all-reduce / AdamW),
-// the weight-gradient launches are DEFERRED: each is queued as a closure that keeps its tensors alive; every VX_WG_FLUSH closures the queue is
-// launched on one side stream behind a single event per launching stream (an event record + wait pair costs ~10 us of host time on this runtime,
-// a pair per convolution made the step slower), so the next layers' backward no longer queues behind ~4 ms of weight-gradient kernels.  The
-// closures (and with them dy, x and the temporaries) are released only after the final join, i.e. after the joining stream waits for the side
-// stream, which is what makes the caching allocator's reuse of that memory safe without record_stream.
-#define VX_WG_FLUSH 8
-struct WgradSide {
+// is needed by the optimizer alone.  While deferral is on (TrainEngine turns it on around the taped backward stages: set_wgrad_defer) the
+// weight-gradient launches are queued as closures that keep their tensors alive; wgrad_join launches each on the stream it was submitted from,
+// behind everything else queued there, so the input gradients that OTHER streams wait for leave it earlier.  (A side stream for them was tried
+// and measured slower: the large weight-gradient grids then take CUs from the critical path.)
+struct WgradQueue {
     bool enabled = false;
-    bool same = false;                 // deferral WITHOUT a side stream: the closures are launched at the join, each on the stream it was submitted from
-    c10::optional<c10::hip::HIPStreamMasqueradingAsCUDA> stream;      // torch on ROCm presents HIP streams with the CUDA device type
     hipEvent_t ev[64] = {};
     unsigned next = 0;
     std::vector<std::pair<void*, std::function<void(void*)>>> pending;      // (stream the operands were produced on, launch closure)
     std::vector<int> pending_dev;                                            // device of each pending closure
-    std::vector<std::function<void(void*)>> done;                            // launched, kept alive until the final join
+    std::vector<std::function<void(void*)>> done;                            // temporaries of the launched closures, kept alive until the join ends
 } WG;
 
 struct AttnFoldPool { std::vector<Tensor> delta, keep; std::vector<float*> dtab; std::vector<VxPwaPlan> plans; };
@@ -132,40 +127,16 @@ inline AttnFoldPool& attn_fold_pool(void* stream, int B, int M) {
     static std::map<std::tuple<void*, int, int>, AttnFoldPool> pools;
     return pools[std::make_tuple(stream, B, M)];
 }
-inline hipStream_t wg_stream(int dev) {
-    if (!WG.stream.has_value()) {
-        WG.stream = c10::hip::getStreamFromPoolMasqueradingAsCUDA(false, (c10::DeviceIndex)dev);
-        for (auto& e : WG.ev) TORCH_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess, "hipEventCreate failed");
-    }
-    return WG.stream->stream();
-}
 inline void wg_order(hipStream_t after, hipStream_t waiter) {           // `waiter` waits for everything enqueued on `after` so far
+    if (WG.ev[0] == nullptr) for (auto& e : WG.ev) TORCH_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess, "hipEventCreate failed");
     hipEvent_t e = WG.ev[WG.next++ & 63];
     TORCH_CHECK(hipEventRecord(e, after) == hipSuccess && hipStreamWaitEvent(waiter, e, 0) == hipSuccess, "wgrad stream ordering failed");
 }
-inline void wg_flush(int dev) {
-    if (WG.pending.empty()) return;
-    hipStream_t side = wg_stream(dev);
-    void* seen[8]; int ns = 0;
-    for (auto& p : WG.pending) {                                         // one event per distinct producing stream
-        bool dup = false;
-        for (int i = 0; i < ns; ++i) dup = dup || seen[i] == p.first;
-        if (!dup) { wg_order((hipStream_t)p.first, side); if (ns < 8) seen[ns++] = p.first; }
-    }
-    {
-        // the closures allocate their temporaries when they are launched: make the side stream current, so that the caching allocator hands out
-        // blocks whose earlier users are ordered before the side stream's kernels (a block of another stream's pool may still be in use there)
-        c10::hip::HIPStreamGuardMasqueradingAsCUDA guard(*WG.stream);
-        for (auto& p : WG.pending) { p.second((void*)side); WG.done.push_back(std::move(p.second)); }
-    }
-    WG.pending.clear(); WG.pending_dev.clear();
-}
-// run `launch(stream)` now on `cur`, or queue it for the side stream
+// run `launch(stream)` now on `cur`, or queue it for wgrad_join
 inline void wgrad_submit(void* cur, int dev, std::function<void(void*)> launch) {
     if (!WG.enabled) { launch(cur); return; }
     WG.pending.emplace_back(cur, std::move(launch));
     WG.pending_dev.push_back(dev);
-    if (!WG.same && WG.pending.size() >= VX_WG_FLUSH) wg_flush(dev);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- convolution
@@ -225,10 +196,9 @@ Tensor conv_fwd_impl(ConvState& st, const Tensor& x_in, const Tensor& x2_in, con
             return y;
         }
         // bf16 storage mode: the patchified copy of the network input (written once, read by this product and by its weight gradient) as a bf16 array on the large grids
-        static const bool patch_h16 = !(getenv("VELOXSEG_BF16_PATCH") && getenv("VELOXSEG_BF16_PATCH")[0] == '0');      // (A/B)
         // (only where the product runs on the 16-byte-per-lane kernel vx_pw_fwd_v4_k -- at most 64 patch channels, one input channel per modality: with BraTS' 256
         // patch channels the one-voxel-per-thread kernel would issue 2-byte loads and the step gets SLOWER: brats128 808 vs 818 patches/s, same box, twice)
-        const bool xs_h16 = patch_h16 && F.act_bf16 && Vo >= 16384 && Vo % 4 == 0 && (K == 2 || K == 4) && Cout % 16 == 0 && Ck <= 64 && Ck % 4 == 0 && Wo % 2 == 0;
+        const bool xs_h16 = F.act_bf16 && Vo >= 16384 && Vo % 4 == 0 && (K == 2 || K == 4) && Cout % 16 == 0 && Ck <= 64 && Ck % 4 == 0 && Wo % 2 == 0;
         Tensor xs = at::empty({B, Ck, Do, Ho, Wo}, xs_h16 ? x.options().dtype(at::kBFloat16) : x.options());
         VX(vx_patchify_bs_h, fp(x), (long)x.stride(0), xs.data_ptr(), B, Cin, Do, Ho, Wo, K, (int)xs_h16, stream);
         if (Vo <= F.pw_mfma_max_v) VX(vx_pw_conv_mfma, fp(xs), nullptr, Ck, fp(w), 0, fp(b), mp(y), nullptr, 0, B, Cout, Ck, Ck, Vo, 0, stream);
@@ -260,8 +230,7 @@ Tensor conv_fwd_impl(ConvState& st, const Tensor& x_in, const Tensor& x2_in, con
                 }
                 if (pre) rc = VXR(vx_expand_fwd_mfma_split_prepared, fp(x), fp(b), fp(wt), mp(y), B, Cout / 64, D, H, W, stream);
                 else rc = VXR(vx_expand_fwd_mfma_split, fp(x), fp(w), fp(b), mp(wt), mp(y), B, Cout / 64, D, H, W, F.expand_split, stream);
-                static const bool ew_on = !(getenv("VELOXSEG_EXPAND_EW_FWD") && getenv("VELOXSEG_EXPAND_EW_FWD")[0] == '0');      // (A/B)
-                st.wt_fwd = (rc == 0 && F.expand_split == 22 && (ew_on || pre) && w.requires_grad()) ? wt : Tensor();
+                st.wt_fwd = (rc == 0 && F.expand_split == 22 && w.requires_grad()) ? wt : Tensor();
             }
             if (rc == 1) rc = vx_expand_fwd_mfma(fp(x), fp(w), fp(b), mp(wt), mp(y), B, Cout / 64, D, H, W, stream);
             if (rc != 0 && rc != 1) chk(rc, "vx_expand_fwd_mfma");
@@ -270,9 +239,8 @@ Tensor conv_fwd_impl(ConvState& st, const Tensor& x_in, const Tensor& x2_in, con
     }
     else if (st.cm) {
         Tensor ws = at::empty({(long)vx_conv_mfma_ws_floats(Cin, Cout, K, 0)}, x.options());
-        static const bool mx_on = !(getenv("VELOXSEG_STEM_ABSMAX_FWD") && getenv("VELOXSEG_STEM_ABSMAX_FWD")[0] == '0');      // (A/B)
         st.xmax = Tensor();
-        if (mx_on && w.requires_grad() && vx_conv_mfma_fwd_writes_absmax(Cin, Cout, D, H, W, K, S, P) == 1) st.xmax = at::empty({1}, x.options().dtype(at::kInt));
+        if (w.requires_grad() && vx_conv_mfma_fwd_writes_absmax(Cin, Cout, D, H, W, K, S, P) == 1) st.xmax = at::empty({1}, x.options().dtype(at::kInt));
         VX(vx_conv_mfma_fwd_mx, fp(x), fp(w), fp(b), mp(y), mp(ws), st.xmax.defined() ? reinterpret_cast<unsigned*>(st.xmax.data_ptr()) : nullptr, B, Cin, D, H, W, Cout, K, S, P, stream);
     }
     else VX(vx_conv3d_fwd, fp(x), fp(x2), C1, fp(w), fp(b), mp(y), B, Cin, D, H, W, Cout, K, S, P, G, ps, stream);
@@ -310,14 +278,14 @@ void conv_bwd_impl(ConvState& st, const Tensor& dy_in, bool need_x, Tensor& dx, 
         }
         return;
     }
-    if (need_x && st.pw && V <= F.pw_mfma_max_v && w.requires_grad() && (!WG.enabled || WG.same) && F.fuse_pw_bwd) {      // both gradients of a small 1x1 conv in one launch
+    if (need_x && st.pw && V <= F.pw_mfma_max_v && w.requires_grad()) {      // both gradients of a small 1x1 conv in one launch
         const int acc = (acc_into.defined() && !x2.defined()) ? 1 : 0;
         dx = acc ? acc_into : at::empty_like(x);
         if (x2.defined()) dx2 = at::empty_like(x2);
         VX(vx_pw_conv_bwd_fused, fp(dy), fp(w), fp(x), fp(x2), C1, mp(dx), mp(dx2), grad_ptr(w), skip_bias ? nullptr : grad_ptr(b), B, Cin, Cout, V, acc, stream);
         return;
     }
-    if (need_x && st.pw && V > F.pw_mfma_max_v && w.requires_grad() && (!WG.enabled || WG.same) && F.fuse_pw_bwd) {     // the same at the large levels
+    if (need_x && st.pw && V > F.pw_mfma_max_v && w.requires_grad()) {     // the same at the large levels
         const int acc = (acc_into.defined() && !x2.defined()) ? 1 : 0;
         dx = acc ? acc_into : at::empty_like(x);
         if (x2.defined()) dx2 = at::empty_like(x2);
@@ -377,7 +345,7 @@ void conv_bwd_impl(ConvState& st, const Tensor& dy_in, bool need_x, Tensor& dx, 
                     WG.done.push_back([xcl](void*) {});          // keeps the temporary alive as long as the launches of this pass
                     VX(vx_expand_wgrad_mfma, fp(x), mp(*xcl), fp(dy), dw, db, B, Cout / 64, D, H, W, s);
                 }
-            } else if (K == 7 && S == 4 && P == 3 && G == 1 && ps == 1 && !x2.defined() && F.use_down_mfma && vx_down_wgrad_ws_floats(B, Cin, D, H, W, Cout) > 0) {
+            } else if (K == 7 && S == 4 && P == 3 && G == 1 && ps == 1 && !x2.defined() && vx_down_wgrad_ws_floats(B, Cin, D, H, W, Cout) > 0) {
                 const int nws = vx_down_wgrad_ws_floats(B, Cin, D, H, W, Cout);          // stem DownConv: MFMA tiles + partial-sum slices
                 auto ws = std::make_shared<Tensor>(at::empty({(long)nws}, x.options()));
                 WG.done.push_back([ws](void*) {});
@@ -1106,7 +1074,7 @@ static std::pair<Tensor, std::shared_ptr<JLCState>> jlc_fwd_f(const Tensor& x, c
         }
         Tensor o = in_fwd_impl(st->in1, x, true, ys, s_);
         Tensor nrm = in_fwd_impl(st->in2, Tensor(), false, {o}, s_);
-        st->fused = F.fuse_gelu && pw_gelu_fusable(nrm, l1w) && l2w.size(1) % 4 == 0;
+        st->fused = pw_gelu_fusable(nrm, l1w) && l2w.size(1) % 4 == 0;
         Tensor h;
         if (st->fused) h = pw_gelu_fwd_impl(st->c1, st->g, nrm, l1w, l1b, 0.0, 0, nullptr, s_);
         else {
@@ -1260,7 +1228,7 @@ static std::pair<Tensor, std::shared_ptr<FFNState>> ffn_fwd_f(const Tensor& y, c
             }
         }
         Tensor n = ln_fwd_impl(st->ln, y, gamma, beta, s_);
-        st->fused = F.fuse_gelu && pw_gelu_fusable(n, w1) && w2.size(1) % 4 == 0;
+        st->fused = pw_gelu_fusable(n, w1) && w2.size(1) % 4 == 0;
         Tensor h;
         if (st->fused) h = pw_gelu_fwd_impl(st->c1, st->g, n, w1, b1, p, site1, sp(rs), s_);
         else {
@@ -1737,66 +1705,38 @@ PYBIND11_MODULE(_vxops, m) {
     m.def("gelu", [](const Tensor& a, double p, int64_t site, int64_t rs) { return GeluFn::apply(a, p, site, rs); });
     m.def("axpy", [](const OptT& x, const Tensor& z, double alpha, double p, int64_t site, int64_t rs) { return AxpyFn::apply(x, z, alpha, p, site, rs); });
 
-    // weight-gradient side stream: enable around the backward pass, join (make `stream` wait for it) before anything reads the parameter gradients
-    m.def("set_wgrad_stream", [](bool on) { WG.enabled = on; });
-    // deferral on the submitting streams (taped encoder backward): the weight-gradient kernels of a stream run after everything else queued on it, so
+    // deferral on the submitting streams (taped backward stages): the weight-gradient kernels of a stream run after everything else queued on it, so
     // the input gradients that OTHER streams wait for leave it earlier; no extra stream competes for CUs.  The closures keep their operands alive.
-    m.def("set_wgrad_defer", [](bool on) { WG.enabled = on; WG.same = on; });
-    m.def("set_wgrad_hold", []() { WG.enabled = false; WG.same = false; });      // stop deferring but KEEP what is queued (a later wgrad_join under set_wgrad_defer launches it)
+    m.def("set_wgrad_defer", [](bool on) { WG.enabled = on; });
+    m.def("set_wgrad_hold", []() { WG.enabled = false; });      // stop deferring but KEEP what is queued (a later wgrad_join launches it)
     // a weight-gradient launch written in python (functional._submit_wgrad: the grouped launch of the fused PWA chains): same queue, same rules.  The
     // callable receives the stream to launch on; it is released under the GIL wherever the queue drops it.
     m.def("wgrad_submit_py", [](int64_t stream, int64_t device, py::function f) {
         std::shared_ptr<py::function> sf(new py::function(std::move(f)), [](py::function* p) { py::gil_scoped_acquire g; delete p; });
         wgrad_submit(sp(stream), (int)device, [sf](void* s) { py::gil_scoped_acquire g; (*sf)((int64_t)(uintptr_t)s); });
     });
-    // spread > 1 (deferral on the submitting streams only): the queued launches are independent sinks, so instead of running one after the other at the
-    // end of the stream they were queued from they are dealt round-robin onto `spread` streams (the submitting stream and spread - 1 forked ones, which
-    // first wait for it); the joining stream waits for all of them.  In a captured stage these become parallel branches, i.e. different tape lanes.
     m.def("wgrad_deferring", []() { return WG.enabled; });
-    m.def("wgrad_join", [](int64_t stream, int64_t device, bool final, int64_t spread) {
-        if (WG.same) {
-            hipStream_t js = (hipStream_t)sp(stream);
-            if (WG.ev[0] == nullptr) for (auto& e : WG.ev) TORCH_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess, "hipEventCreate failed");
-            static std::vector<c10::hip::HIPStreamMasqueradingAsCUDA> sides;
-            const int nsp = (int)std::max<int64_t>(1, std::min<int64_t>(spread, 4));
-            while ((int)sides.size() < nsp - 1) sides.push_back(c10::hip::getStreamFromPoolMasqueradingAsCUDA(false, (c10::DeviceIndex)device));
-            void* seen[8]; int ns = 0;
-            std::vector<std::pair<void*, int>> forked;                    // (submitting stream, side index) pairs already ordered
-            bool side_used[4] = {false, false, false, false};
-            for (size_t i = 0; i < WG.pending.size(); ++i) {
-                auto& p = WG.pending[i];
-                const int k = nsp > 1 ? (int)(i % (size_t)nsp) : 0;
-                const c10::DeviceIndex dev = (c10::DeviceIndex)(i < WG.pending_dev.size() ? WG.pending_dev[i] : device);
-                if (k == 0) {
-                    // the closure allocates its temporaries (partial-sum slices, a channels-last copy) when it is launched.  They must come from
-                    // the pool of the stream the kernels run on: a cached block of the CALLER's stream may still be in use by kernels queued on
-                    // it, which the launch stream does not wait for (seen as a corrupted level-1 attention backward, brats128 B=4, eager stages)
-                    auto ls = p.first ? c10::hip::getStreamFromExternalMasqueradingAsCUDA((hipStream_t)p.first, dev) : c10::hip::getDefaultHIPStreamMasqueradingAsCUDA(dev);
-                    c10::hip::HIPStreamGuardMasqueradingAsCUDA guard(ls);
-                    p.second(p.first);
-                    bool dup = p.first == (void*)js;
-                    for (int j = 0; j < ns; ++j) dup = dup || seen[j] == p.first;
-                    if (!dup && ns < 8) seen[ns++] = p.first;
-                } else {
-                    auto& side = sides[k - 1];
-                    bool ordered = false;
-                    for (auto& f : forked) ordered = ordered || (f.first == p.first && f.second == k);
-                    if (!ordered) { wg_order((hipStream_t)p.first, side.stream()); forked.emplace_back(p.first, k); }
-                    c10::hip::HIPStreamGuardMasqueradingAsCUDA guard(side);
-                    p.second((void*)side.stream());
-                    side_used[k] = true;
-                }
-            }
-            for (int j = 0; j < ns; ++j) wg_order((hipStream_t)seen[j], js);      // the joining stream waits for the streams that got late work
-            for (int k = 1; k < nsp; ++k) if (side_used[k]) wg_order(sides[k - 1].stream(), js);
-            WG.pending.clear(); WG.pending_dev.clear();
-            WG.done.clear();
-            return;
+    // launch what is queued, each closure on the stream it was submitted from; `stream` then waits for every stream that got late work
+    m.def("wgrad_join", [](int64_t stream, int64_t device) {
+        hipStream_t js = (hipStream_t)sp(stream);
+        void* seen[8]; int ns = 0;
+        for (size_t i = 0; i < WG.pending.size(); ++i) {
+            auto& p = WG.pending[i];
+            const c10::DeviceIndex dev = (c10::DeviceIndex)(i < WG.pending_dev.size() ? WG.pending_dev[i] : device);
+            // the closure allocates its temporaries (partial-sum slices, a channels-last copy) when it is launched.  They must come from
+            // the pool of the stream the kernels run on: a cached block of the CALLER's stream may still be in use by kernels queued on
+            // it, which the launch stream does not wait for (seen as a corrupted level-1 attention backward, brats128 B=4, eager stages)
+            auto ls = p.first ? c10::hip::getStreamFromExternalMasqueradingAsCUDA((hipStream_t)p.first, dev) : c10::hip::getDefaultHIPStreamMasqueradingAsCUDA(dev);
+            c10::hip::HIPStreamGuardMasqueradingAsCUDA guard(ls);
+            p.second(p.first);
+            bool dup = p.first == (void*)js;
+            for (int j = 0; j < ns; ++j) dup = dup || seen[j] == p.first;
+            if (!dup && ns < 8) seen[ns++] = p.first;
         }
-        wg_flush((int)device);
-        if (WG.stream.has_value() && !WG.done.empty()) wg_order(WG.stream->stream(), (hipStream_t)sp(stream));
-        if (final) WG.done.clear();          // after the wait above: the memory may be reused by the joining stream
-    }, py::arg("stream"), py::arg("device"), py::arg("final"), py::arg("spread") = 0);
+        for (int j = 0; j < ns; ++j) wg_order((hipStream_t)seen[j], js);
+        WG.pending.clear(); WG.pending_dev.clear();
+        WG.done.clear();
+    }, py::arg("stream"), py::arg("device"));
 
     // kernel pass of bench.py: every C-ABI call made from this module between profile_begin() and profile_end() is timed with HIP events on its
     // launch stream; profile_end() -> [(entry, (small integer arguments...), ms)]
@@ -1831,13 +1771,10 @@ PYBIND11_MODULE(_vxops, m) {
     m.def("set_jlc_tile", [](bool on) { F.jlc_tile = on; });      // A/B (tests): JLC block of the coarse levels fused (default) or per operator
     m.def("set_expand_wgrad_split", [](bool on) { F.expand_wgrad_split = on; });      // A/B (tests, probes): weight gradient of the patch-expand layers on the split kernels
     m.def("set_fuse_blocks", [](bool on) { F.fuse_blocks = on; });     // A/B: JLC block / FFN tail on the fused block kernels (jlc.hip, mlp.hip) vs the per-operator kernels
-    m.def("set_fuse_gelu", [](bool on) { F.fuse_gelu = on; });
     m.def("set_fuse_bwd_add", [](bool on) { F.fuse_bwd_add = on; });   // A/B: residual-gradient sums in the stores of the InstanceNorm / LayerNorm backward kernels
     m.def("set_fuse_res", [](bool on) { F.fuse_res = on; });           // A/B: residual + dropout in the epilogue of the second 1x1 conv of the JLC / FFN stage
     m.def("set_in_split2", [](bool on) { F.in_split2 = on; });         // A/B: long-row InstanceNorm in 2 launches per direction (0 = separate stats / finalise / apply launches)
     m.def("set_skip_in_bias", [](bool on) { F.skip_in_bias = on; });   // A/B: 0 = compute the (mathematically zero) bias gradients of convs that feed an InstanceNorm
-    m.def("set_down_mfma", [](bool on) { F.use_down_mfma = on; });  // A/B: MFMA weight gradient of the k7 s4 stem conv
-    m.def("set_fuse_pw_bwd", [](bool on) { F.fuse_pw_bwd = on; });  // A/B: input + weight gradient of small 1x1 convs in one launch      // A/B: GELU (+ dropout) in the 1x1 conv epilogues of the JLC / FFN composites
 
     m.def("conv_fwd", [](const Tensor& x, const OptT& x2, const Tensor& w, const OptT& b, int K, int S, int P, int G, int ps, int64_t stream) {
         auto st = std::make_shared<ConvState>();

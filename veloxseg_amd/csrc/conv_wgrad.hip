@@ -837,11 +837,8 @@ __global__ void __launch_bounds__(256) vx_stem_wgrad_f16_k(const float* __restri
         if (G == 0) atomicAdd(db + n, bsum);
     }
 }
-static int vx_stem_wg_f16 = -1;
-static int stem_wg_f16_on() {
-    if (vx_stem_wg_f16 < 0) { const char* e = getenv("VELOXSEG_STEM_WG_F16"); vx_stem_wg_f16 = e ? atoi(e) : 1; if (vx_stem_wg_f16 < 0) vx_stem_wg_f16 = 0; }
-    return vx_stem_wg_f16;
-}
+static int vx_stem_wg_f16 = 1;
+static int stem_wg_f16_on() { return vx_stem_wg_f16; }
 extern "C" int vx_down_wgrad_set_f16(int on) { vx_stem_wg_f16 = on ? 1 : 0; return 0; }      // A/B knob (tests): the stem weight gradient on the f16 pipe (default) or the fp32 MFMA kernel
 static bool stem_wg_f16_ok(int Cin, int Di, int Hi, int Wi, int Cout) { return Cout == 16 && (Wi == 128 || Wi == 96 || Wi == 64) && Hi % 16 == 0 && Di % 4 == 0 && Cin >= 1 && Cin <= 8; }
 
@@ -1020,10 +1017,9 @@ __global__ void __launch_bounds__(256) vx_wgrad_gather_mfma_k(VxGw p) {
         }
     }
 }
-static int vx_wg_gather = -1;
+static int vx_wg_gather = 1;
 extern "C" int vx_conv_wgrad_gather_set(int on) { vx_wg_gather = on ? 1 : 0; return 0; }       // A/B knob (tests)
 extern "C" int vx_conv_wgrad_gather_ok(int B, int Cin, int Di, int Hi, int Wi, int Cout, int K, int S, int P) {
-    if (vx_wg_gather < 0) { const char* e = getenv("VELOXSEG_WGRAD_GATHER"); vx_wg_gather = e ? atoi(e) : 1; }
     if (!vx_wg_gather || B <= 0 || Cin <= 0 || K < 1 || K > 5 || S < 1 || P < 0) return 0;
     if (Cout != 32 && Cout != 64 && Cout != 128) return 0;
     const int Do = (Di + 2 * P - K) / S + 1, Ho = (Hi + 2 * P - K) / S + 1, Wo = (Wi + 2 * P - K) / S + 1;
@@ -1132,11 +1128,10 @@ __global__ void __launch_bounds__(256) vx_jlc_wgrad_gather_k(VxJg p) {
         }
     }
 }
-static int vx_jg_on = -1;
-static long vx_jg_max_v = 512;
+static int vx_jg_on = 1;
+static constexpr long vx_jg_max_v = 512;
 extern "C" int vx_jlc_wgrad_gather_set(int on) { vx_jg_on = on ? 1 : 0; return 0; }      // A/B knob (tests)
 extern "C" int vx_jlc_wgrad_gather_ok(int C, int G, int D, int H, int W) {
-    if (vx_jg_on < 0) { const char* e = getenv("VELOXSEG_JLC_WG_GATHER"); vx_jg_on = e ? atoi(e) : 1; const char* m = getenv("VELOXSEG_JLC_WG_GATHER_MAX_V"); if (m) vx_jg_max_v = atol(m); }
     if (!vx_jg_on || C <= 0 || G <= 0 || C % G) return 0;
     const int CG = C / G;
     return ((CG == 8 || CG == 16 || CG == 4) && (long)D * H * W <= vx_jg_max_v && D > 0 && H > 0 && W > 0) ? 1 : 0;

@@ -975,8 +975,6 @@ __global__ void __launch_bounds__(256) vx_expand_wmax_k(const float* __restrict_
 __device__ __forceinline__ int vx_expand_wexp(const float* __restrict__ ew) { return vx_exp16(__uint_as_float(reinterpret_cast<const unsigned*>(ew)[1])); }
 // returns the number of partial maxima left at ew + 4 (<= 64): the argument `nparts` of vx_expand_wimg_f16_k
 static inline int vx_expand_wmax_launch(const float* w, long n, float* ew, hipStream_t st) {
-    static const bool ms = getenv("VELOXSEG_EXPAND_WMAX_MEMSET") && getenv("VELOXSEG_EXPAND_WMAX_MEMSET")[0] == '1';      // (A/B: the memset node of rounds 4 - 5 back in front; results unchanged)
-    if (ms && hipMemsetAsync(ew, 0, 2 * sizeof(float), st) != hipSuccess) return 1;
     int nb = (int)((n / 4 + 255) / 256);
     if (nb > 64) nb = 64;
     if (nb < 1) nb = 1;
@@ -1576,7 +1574,7 @@ __global__ void __launch_bounds__(256) vx_expand_wgrad_fold_k(const float* __res
 static void vx_wgs_plan(int B, int Cc, int D, int H, int W, int& HL, int& nHs, int& nWc) {
     nWc = (W + 31) / 32;
     const long base = (long)B * D * nWc * Cc * 3;
-    static const long target = getenv("VELOXSEG_EXPAND_WG_BLOCKS") ? atol(getenv("VELOXSEG_EXPAND_WG_BLOCKS")) : 384;      // (round 6 A/B, same box: 768 -> 384 blocks for the one-channel decoders -- half the partial-sum rows -- autopet128 1051.6 -> 1056.4, autopet96 +0.4 %, hecktor -0.2 %; this kernel is a sink beside the encoder backward)
+    constexpr long target = 384;      // (round 6 A/B, same box: 768 -> 384 blocks for the one-channel decoders -- half the partial-sum rows -- autopet128 1051.6 -> 1056.4, autopet96 +0.4 %, hecktor -0.2 %; this kernel is a sink beside the encoder backward)
     int want = (int)((target + base - 1) / base);            // strips per (b, d, chunk, c, plane)
     if (want < 1) want = 1;
     HL = (H + want - 1) / want;

@@ -656,9 +656,7 @@ static int tz_plan(VxTz& p, TzPlan& pl, int B, int C, int G, int D, int H, int W
     const int CG = C / G;
     if (CG != 4 && CG != 8 && CG != 16) return -1;
     p.B = B; p.C = C; p.G = G; p.D = D; p.H = H; p.W = W;
-    static int td_env = -1, th_env = -1;
-    if (td_env < 0) { const char* e = getenv("VELOXSEG_TZ_TD"); td_env = e ? atoi(e) : 0; const char* e2 = getenv("VELOXSEG_TZ_TH"); th_env = e2 ? atoi(e2) : 0; }
-    const int tdm = td_env > 0 ? td_env : 8, thm = th_env > 0 ? th_env : 8;
+    constexpr int tdm = 8, thm = 8;
     p.TWB = W / 4 < 8 ? W / 4 : 8;
     p.TH = H < thm ? H : thm;
     p.TD = D < tdm ? D : tdm;
@@ -1271,12 +1269,9 @@ __global__ void __launch_bounds__(SPEC ? 512 : 256, SPEC ? 1 : 2) vx_jlc_wg_k(Vx
 
 static int g_wg_blocks = 0;
 extern "C" int vx_jlc_wgrad_tz_set_blocks(int n) { g_wg_blocks = n > 0 ? n : 0; return 0; }      // blocks per launch (0: the default rule in wg_plan)
-static int g_wg_spec = -1;
-extern "C" int vx_jlc_wgrad_tz_set_spec(int on) { g_wg_spec = on ? 1 : 0; return 0; }      // A/B: producer / consumer waves (default on; VELOXSEG_WG_SPEC)
-static bool wg_spec_on() {
-    if (g_wg_spec < 0) { const char* e = getenv("VELOXSEG_WG_SPEC"); g_wg_spec = (e && e[0] == '0') ? 0 : 1; }
-    return g_wg_spec == 1;
-}
+static int g_wg_spec = 1;
+extern "C" int vx_jlc_wgrad_tz_set_spec(int on) { g_wg_spec = on ? 1 : 0; return 0; }      // A/B: producer / consumer waves (default on)
+static bool wg_spec_on() { return g_wg_spec == 1; }
 static int wg_plan(VxWgT& p, size_t& shm, int B, int C, int G, int D, int H, int W, int NS, bool spec = false) {
     if (B <= 0 || C <= 0 || G <= 0 || C % G || D <= 0 || H <= 0 || W <= 0 || (W & 3) || (H & 3) || W > 32) return -1;
     const int CG = C / G;
@@ -1285,9 +1280,7 @@ static int wg_plan(VxWgT& p, size_t& shm, int B, int C, int G, int D, int H, int
     p.WS = (W + 7) / 8 * 8;
     p.nb = 32 / p.WS;
     p.nsg = vx_cdiv(B, p.nb);
-    static int th_env = -1;
-    if (th_env < 0) { const char* e = getenv("VELOXSEG_WG_TZ_TH"); th_env = e ? atoi(e) : 0; }
-    p.TH = (H % 8 == 0 && th_env != 4) ? 8 : 4;       // (12-row tiles would need more than WG_NPF staging items per thread)
+    p.TH = H % 8 == 0 ? 8 : 4;       // (12-row tiles would need more than WG_NPF staging items per thread)
     p.nHt = H / p.TH;
     p.nXB = p.TH / 4 + 1;
     p.XR = p.WS + 8;
@@ -1298,26 +1291,21 @@ static int wg_plan(VxWgT& p, size_t& shm, int B, int C, int G, int D, int H, int
     p.SP = p.GB + (p.R5 + p.R3 + p.R1) * p.GP;
     const int MT = CG / 4;
     const long base_blocks = (long)p.nsg * G * MT * MT * p.nHt;
-    static int target_env = -1;
-    if (target_env < 0) { const char* e = getenv("VELOXSEG_WG_TZ_BLOCKS"); target_env = (e && atoi(e) > 0) ? atoi(e) : 0; }
     // Default: 128 blocks (HALF the chip) with producer / consumer waves, 256 for the one-role kernel.  With the producer waves a launch on 128 CUs takes what the one-role
     // kernel took on 256 (53.7 vs 52.8 us average), and what the sink leaves free is what the other lanes' chains use: 1040 patches/s against 1021 with 256 blocks (where
-    // the kernel alone is 42.7 us: bench.py reports that figure as roofline.full_chip) and 1027 for the one-role kernel.  vx_jlc_wgrad_tz_set_blocks / VELOXSEG_WG_TZ_BLOCKS.
-    const int target = g_wg_blocks > 0 ? g_wg_blocks : (target_env > 0 ? target_env : (spec ? 128 : 256));
+    // the kernel alone is 42.7 us: bench.py reports that figure as roofline.full_chip) and 1027 for the one-role kernel.  vx_jlc_wgrad_tz_set_blocks.
+    const int target = g_wg_blocks > 0 ? g_wg_blocks : (spec ? 128 : 256);
     // Blocks per launch: 256 = one per CU.  Stand-alone, 512 (two resident blocks per CU, one's staging behind the other's MFMAs) is faster (67 vs 84 us at 32^3), but
     // this kernel is a SINK that runs beside the backward chains of the other lanes: at 74 KB of LDS and 248 VGPRs per block, two blocks per CU leave those chains
-    // nothing to run on -- the step is 774 patches/s with 512 blocks, 798 with 256, 782 with the VALU weight-gradient kernels (VELOXSEG_WG_TZ_BLOCKS for the A/B)
+    // nothing to run on -- the step is 774 patches/s with 512 blocks, 798 with 256, 782 with the VALU weight-gradient kernels (vx_jlc_wgrad_tz_set_blocks for the A/B)
     int nchunks = (int)((target + base_blocks - 1) / base_blocks);
     // at least two owned planes per chunk (a chunk walks its planes + 4: one-plane chunks do 5 steps for one plane's work).  On the 8-plane level one plane per chunk
-    // (VELOXSEG_WG_TZ_MINDC8=1: 256 blocks instead of 128) is FASTER ALONE -- 31.9 vs 39.2 us, tools/jlc_wg_probe.py -- and SLOWER IN THE STEP (1020 vs 1028 patches/s,
+    // (256 blocks instead of 128) is FASTER ALONE -- 31.9 vs 39.2 us, tools/jlc_wg_probe.py -- and SLOWER IN THE STEP (1020 vs 1028 patches/s,
     // same box, twice): this kernel is a sink beside the other lanes' chains, and what it costs them is CUs, not microseconds (as with 512 blocks at 32^3 in round 4)
-    static int mindc8 = 0;
-    if (!mindc8) { const char* e = getenv("VELOXSEG_WG_TZ_MINDC8"); mindc8 = (e && atoi(e) == 1) ? 1 : 2; }
-    const int min_dc = D <= 8 ? mindc8 : 2;
+    constexpr int min_dc = 2;
     if (nchunks > D / min_dc) nchunks = D / min_dc;
     if (nchunks < 1) nchunks = 1;
     p.DC = vx_cdiv(D, nchunks);
-    { static int dc_env = -1; if (dc_env < 0) { const char* e = getenv("VELOXSEG_WG_TZ_DC"); dc_env = e ? atoi(e) : 0; } if (dc_env > 0 && dc_env <= D) p.DC = dc_env; }      // (experiments)
     p.nDc = vx_cdiv(D, p.DC);
     if ((long)p.nb * 4 * (p.TH + 4) * (p.XR / 4) + 3L * p.nb * 4 * p.TH * (p.WS / 4) > (long)WG_NPF * 256) return -1;      // one step's staging list must fit the per-thread items
     shm = (size_t)NS * p.SP * 2 + 128;              // (+ the maxima / exponent tables of the fp16 mode)
@@ -1326,14 +1314,13 @@ static int wg_plan(VxWgT& p, size_t& shm, int B, int C, int G, int D, int H, int
     return 0;
 }
 
-static long g_wg_min_v = -1;
+static long g_wg_min_v = 0;
 static int g_wg_f16 = 0;
 extern "C" int vx_jlc_wgrad_tz_set_f16(int on) { g_wg_f16 = on ? 1 : 0; return 0; }
 extern "C" int vx_jlc_wgrad_tz_set_min_voxels(long v) { g_wg_min_v = v < 0 ? 0 : v; return 0; }
 extern "C" int vx_jlc_wgrad_tz_ok(int C, int G, int D, int H, int W) {
     VxWgT p = {};
     size_t shm;
-    if (g_wg_min_v < 0) { const char* e = getenv("VELOXSEG_WG_TZ_MIN_V"); g_wg_min_v = e ? atol(e) : 0; }
     if ((long)D * H * W < g_wg_min_v) return 0;
     return wg_plan(p, shm, 1, C, G, D, H, W, tz_pieces() == 22 ? 3 : tz_pieces()) == 0 ? 1 : 0;
 }
@@ -1345,10 +1332,8 @@ extern "C" int vx_jlc_wgrad_tz(const float* x, const float* g1, const float* g3,
     size_t shm;
     // pieces = 22 (two scaled fp16 pieces): the weight-gradient kernel has that mode too (per-plane exponents, exact accumulator rescaling), but it is 4 us SLOWER at
     // 32^3 than three bf16 pieces (68 vs 64 us): the MFMAs are 16 of the kernel's 64 us, and the per-step maxima + the extra barrier cost more than halving them
-    // saves.  VELOXSEG_WG_TZ_F16=1 selects it (A/B, tests); default: three bf16 pieces.
-    static int wg16 = -1;
-    if (wg16 < 0) { const char* e = getenv("VELOXSEG_WG_TZ_F16"); wg16 = (e && e[0] == '1') ? 1 : 0; }
-    const bool f16 = tz_pieces() == 22 && (wg16 == 1 || g_wg_f16 == 1);
+    // saves.  vx_jlc_wgrad_tz_set_f16(1) selects it (A/B, tests); default: three bf16 pieces.
+    const bool f16 = tz_pieces() == 22 && g_wg_f16 == 1;
     const int NS = f16 ? 2 : (tz_pieces() == 22 ? 3 : tz_pieces());
     VX_REQUIRE(!t_tz_h16 || NS == 1, "vx_jlc_wgrad_tz: 16-bit g_k need plain bf16 operands (pieces = 1, the bf16 mode)");
     // producer / consumer waves: the default (three bf16 pieces) instance, when its deeper staging (two x buffers, one more slot per ring) fits

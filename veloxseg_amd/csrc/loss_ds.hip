@@ -56,7 +56,7 @@ struct VxDs {
     int nh, B, D, H, W;
     int stage;                  // 1: the Z-interpolated slices of a sample's grids are staged in LDS (they fit); 0: 8 taps gathered from global memory
     int nsplit;                 // forward: blocks per Z slice
-    int dbg;                    // timing experiments (VX_DS_DBG): bit 0 no final atomics, bit 1 no low-resolution heads
+    int dbg;                    // timing experiments (always 0 in the library): bit 0 no final atomics, bit 1 no low-resolution heads
     float rh[3], rw[3];         // column-owner kernels: (h - 1) / (H - 1), (w - 1) / (W - 1) of heads 1.. (the quotient vx_ds_coord forms, computed once on the host)
 };
 
@@ -468,7 +468,7 @@ __global__ void __launch_bounds__(256) vx_seg_loss_ds_adj_z_k(VxDsZ P) {
 //   * backward: the ADJOINT of that interpolation is the transposed matrix: the quad's gradient collapses to NK column sums (registers), which are accumulated over
 //     the thread's consecutive rows in two register rows (coarse rows a1 and a1 + 1) and flushed to the wave's LDS accumulators with ds_add_f32 only when a1 advances
 //     (every 1 / scale rows): ~40 LDS atomics per thread and slice replace the gradient staging buffer, the band tables and their ~300 dependent LDS round trips per step.
-// Everything else (soft-max arithmetic, accumulator layout, the D adjoint behind it) is unchanged; vx_seg_loss_ds_set_columns(0) / VELOXSEG_DS_COLUMNS=0 selects the
+// Everything else (soft-max arithmetic, accumulator layout, the D adjoint behind it) is unchanged; vx_seg_loss_ds_set_columns(0) selects the
 // row-sweep kernels above.
 template <int NK>
 __device__ __forceinline__ void vx_ds_col_setup(int X0, int wl, float ratio, int& i0, float (&cw)[4][NK]) {
@@ -863,10 +863,9 @@ __global__ void __launch_bounds__(256) vx_seg_loss_ds_bwd_col_k(VxDs P, const vo
 
 // does the column-owner map cover this geometry?  W/4 <= 64, every head narrower than the volume, and a quad never touching more than NK coarse columns
 // (returns NK = 3 or 4, or 0)
-static int g_ds_columns = -1;
+static int g_ds_columns = 1;
 extern "C" int vx_seg_loss_ds_set_columns(int on) { g_ds_columns = on ? 1 : 0; return 0; }
 static int vx_ds_columns_nk(const VxDs& P) {
-    if (g_ds_columns < 0) { const char* e = getenv("VELOXSEG_DS_COLUMNS"); g_ds_columns = (e && e[0] == '0') ? 0 : 1; }
     if (!g_ds_columns || P.nh < 2) return 0;
     const int W4 = P.W >> 2;
     if (W4 <= 0 || W4 > 64) return 0;          // (W/4 = 24 / 12 -- the 96^3 patches: 256 / (W/4) row groups, the block's last 256 % (W/4) threads get no rows)
@@ -943,12 +942,9 @@ extern "C" int vx_seg_loss_ds_fwd(const float* l0, const float* l1, const float*
     const int nk = P.stage ? vx_ds_columns_nk(P) : 0;
     const size_t shm_col = vx_ds_slice_pad_floats(P, C) * sizeof(float);
     if (nk && shm_col <= 48 * 1024) {          // column-owner map (see above)
-        // two blocks per slice (VELOXSEG_DS_FWD_SPLIT; measured at 128^3 x 4: 1 / 2 / 4 parts = 64 / 61 / 91 us): a thread's set-up (column weights) is amortised over
+        // two blocks per slice (measured at 128^3 x 4: 1 / 2 / 4 parts = 64 / 61 / 91 us): a thread's set-up (column weights) is amortised over
         // its rows, and every block ends in ~20 double atomics on the same few accumulators
-        static int fsplit = -1;
-        if (fsplit < 0) { const char* e = getenv("VELOXSEG_DS_FWD_SPLIT"); fsplit = e ? atoi(e) : 2; if (fsplit < 1 || fsplit > 8) fsplit = 2; }
-        P.nsplit = fsplit;
-        { const char* e = getenv("VX_DS_DBG"); P.dbg = e ? atoi(e) : 0; }
+        P.nsplit = 2;
         const dim3 grid(D * P.nsplit, B);
 #define VX_DS_FWD_COL(CC)                                                                                                              \
         { if (t_ds_h16) { if (nk == 3) vx_seg_loss_ds_fwd_col_k<CC, 3, vx_bf16><<<grid, blk, shm_col, st>>>(P, labels, lab_kind, acc);            \
@@ -967,17 +963,12 @@ extern "C" int vx_seg_loss_ds_fwd(const float* l0, const float* l1, const float*
     return 0;
 }
 
-// workspace (floats) of vx_seg_loss_ds_bwd: the (B, C, D x row parts, h, w) partial gradients of heads 1.., sized for the ACTIVE split (resolved once per process:
-// 1 by default; VELOXSEG_DS_BWD_SPLIT is an A/B knob that measured slower overall -- sizing for its maximum held 8 x the memory inside the capture pools)
-#define VX_DS_MAX_SPLIT 8
-static int ds_bwd_split() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VELOXSEG_DS_BWD_SPLIT"); const int u = e ? atoi(e) : 1; v = (u >= 1 && u <= VX_DS_MAX_SPLIT) ? u : 1; }
-    return v;
-}
+// workspace (floats) of vx_seg_loss_ds_bwd: the (B, C, D x row parts, h, w) partial gradients of heads 1.., sized for the one row part per slice the backward
+// runs with (more parts measured slower overall, see vx_seg_loss_ds_bwd)
+static constexpr int DS_BWD_SPLIT = 1;
 extern "C" int vx_seg_loss_ds_ws_floats(const int* low_dims, int nh, int B, int C, int D) {
     long n = 0;
-    for (int hh = 0; hh < nh - 1; ++hh) n += (long)B * C * D * ds_bwd_split() * low_dims[3 * hh + 1] * low_dims[3 * hh + 2];
+    for (int hh = 0; hh < nh - 1; ++hh) n += (long)B * C * D * DS_BWD_SPLIT * low_dims[3 * hh + 1] * low_dims[3 * hh + 2];
     VX_REQUIRE(n < 0x7fffffffL, "vx_seg_loss_ds_ws_floats: workspace too large");
     return (int)n;
 }
@@ -1000,16 +991,14 @@ extern "C" int vx_seg_loss_ds_bwd(const float* l0, const float* l1, const float*
         for (int k = 0; k < 3; ++k) Zp.ld[hh][k] = P.ld[hh][k];
         Zp.n[hh] = (long)B * C * P.ld[hh][0] * P.ld[hh][1] * P.ld[hh][2];
         total += Zp.n[hh];
-        off += (long)B * C * D * ds_bwd_split() * P.ld[hh][1] * P.ld[hh][2];
+        off += (long)B * C * D * DS_BWD_SPLIT * P.ld[hh][1] * P.ld[hh][2];
         nacc += C * P.ld[hh][1] * P.ld[hh][2];          // (two classes + staged slices: the kernel uses half of it)
     }
     const int RPW = 64 / (W >> 2);
     // blocks per Z slice (row parts): a block is one long serial program per wave (soft-max side, then the W / H adjoints through LDS) -- with one block per slice the
     // 128^3 x 4 patch is 512 blocks = 2 waves per SIMD and the kernel waits on its LDS round trips (198 us); every part keeps >= 2 steps of 4 waves x RPW rows
-    P.nsplit = 1;
-    // (measured, 128^3 x 4: 1 / 4 parts = 181 / 158 us, but the D adjoint behind it then reads 4 x the partial sums: 20 -> 57 us -- the default stays at one part)
-    if (H / ds_bwd_split() >= 1) P.nsplit = ds_bwd_split();          // (the workspace above is laid out for exactly this many parts)
-    else VX_FAIL(-1, "vx_seg_loss_ds_bwd: VELOXSEG_DS_BWD_SPLIT=%d exceeds the %d rows of a slice", ds_bwd_split(), H);
+    // (measured, 128^3 x 4: 1 / 4 parts = 181 / 158 us, but the D adjoint behind it then reads 4 x the partial sums: 20 -> 57 us -- it stays at one part)
+    P.nsplit = DS_BWD_SPLIT;          // (the workspace above is laid out for exactly this many parts)
     Zp.nlow = nh - 1; Zp.BC = B * C; Zp.D = D; Zp.nsplit = P.nsplit;
     size_t ntab = 0;
     for (int hh = 0; hh < nh - 1; ++hh) {

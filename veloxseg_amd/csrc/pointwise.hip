@@ -504,9 +504,8 @@ __global__ void __launch_bounds__(256) vx_patch4_wgrad_k(const float* __restrict
 
 // 1 where the fused patch embedding takes the layer (callers fall back to vx_patchify + the 1x1 kernels elsewhere: other patch sizes, ragged rows, tiny grids)
 extern "C" int vx_patch_embed_ok(int Cin, int Cout, int Do, int Ho, int Wo, int K) {
-    static const int off = getenv("VELOXSEG_PATCH_FUSED") && getenv("VELOXSEG_PATCH_FUSED")[0] == '0';      // (A/B)
-    static const long minv = getenv("VELOXSEG_PATCH_FUSED_MINV") ? atol(getenv("VELOXSEG_PATCH_FUSED_MINV")) : 8192;
-    return (!off && K == 4 && Cin >= 1 && Cin <= 8 && Cout % 16 == 0 && Wo % 4 == 0 && Do > 0 && Ho > 0 && (long)Do * Ho * Wo >= minv) ? 1 : 0;
+    constexpr long minv = 8192;
+    return (K == 4 && Cin >= 1 && Cin <= 8 && Cout % 16 == 0 && Wo % 4 == 0 && Do > 0 && Ho > 0 && (long)Do * Ho * Wo >= minv) ? 1 : 0;
 }
 // y[b, co, z, y, x] = bias[co] + sum w[co, cin, kd, kh, kw] * x[b, cin, 4z + kd, 4y + kh, 4x + kw];  batch_stride: floats between the samples of x (a channel slice
 // of a wider tensor is read in place)
@@ -530,8 +529,8 @@ extern "C" int vx_patch_embed_bwd_weight(const float* x, long batch_stride, cons
     const long NQ = (long)B * Do * Ho * Wo / 4;
     const int nbx = Cin * 4 * (Cout / 16);
     // chunks: about 1024 blocks in all, at least 2 quads per lane, a multiple of 8 chunks (vx_xcd_rows)
-    static const long blocks_env = getenv("VELOXSEG_PATCH_WG_BLOCKS") ? atol(getenv("VELOXSEG_PATCH_WG_BLOCKS")) : 256;      // (A/B)
-    long chunks = blocks_env / nbx;
+    constexpr long blocks = 256;
+    long chunks = blocks / nbx;
     if (chunks > NQ / 128) chunks = NQ / 128;
     chunks = chunks / 8 * 8;
     if (chunks < 8) chunks = 8;
@@ -964,9 +963,7 @@ extern "C" int vx_pw_wgrad_group(const void* const* ptrs, const long* dims, int 
         J.Cin = (int)dims[4 * k]; J.Cout = (int)dims[4 * k + 1]; J.V = dims[4 * k + 2]; J.B = (int)dims[4 * k + 3];
         VX_REQUIRE(J.x && J.dy && J.dw && J.Cin > 0 && J.Cout > 0 && J.V > 0 && J.B > 0, "vx_pw_wgrad_group: bad job %d", k);
         const int mt = vx_cdiv(J.Cout, 16), nt = vx_cdiv(J.Cin, 16);
-        static int wgg_waves = -1, wgg_minv = -1;
-        if (wgg_waves < 0) { const char* e = getenv("VELOXSEG_WGG_WAVES"); wgg_waves = (e && atoi(e) > 0) ? atoi(e) : 1024; }
-        if (wgg_minv < 0) { const char* e = getenv("VELOXSEG_WGG_MINV"); wgg_minv = (e && atoi(e) > 0) ? atoi(e) : 256; }
+        constexpr int wgg_waves = 1024, wgg_minv = 256;
         long waves_per_tile = wgg_waves / ((long)mt * nt);
         if (waves_per_tile < 4) waves_per_tile = 4;
         long vpw = ((long)J.B * J.V + waves_per_tile - 1) / waves_per_tile;
@@ -986,14 +983,6 @@ extern "C" int vx_pw_wgrad_group(const void* const* ptrs, const long* dims, int 
         blk += F.nblk;
     }
     VX_REQUIRE(blk < 0x7fffffffL, "vx_pw_wgrad_group: grid too large");
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("VX_WGG_DBG"); dbg = (e && e[0] == '1') ? 1 : 0; }
-    if (dbg) {
-        fprintf(stderr, "[wgg] %d jobs %d folds %ld blocks:", nj, nf, blk);
-        for (int k = 0; k < nj; ++k) fprintf(stderr, " (%d->%d V=%ld B=%d vpw=%d blk=%d)", g.j[k].Cin, g.j[k].Cout, g.j[k].V, g.j[k].B, g.j[k].vpw, g.j[k].nblk);
-        for (int k = 0; k < nf; ++k) fprintf(stderr, " [fold C=%d rows=%d]", g.f[k].C, g.f[k].rows);
-        fprintf(stderr, "\n");
-    }
     vx_pw_wgrad_group_k<<<dim3((unsigned)blk), 256, 0, (hipStream_t)stream>>>(g);
     VX_LAUNCH_CHECK("vx_pw_wgrad_group");
     return 0;
@@ -1183,10 +1172,9 @@ __global__ void __launch_bounds__(256) vx_upconv_mfma4_k(const float* __restrict
         }
     }
 }
-static int vx_upconv_mfma4_on = -1;
+static int vx_upconv_mfma4_on = 1;
 extern "C" int vx_upconv_set_mfma4(int on) { vx_upconv_mfma4_on = on ? 1 : 0; return 0; }
 static bool vx_upconv_mfma4_ok(int wd) {
-    if (vx_upconv_mfma4_on < 0) { const char* e = getenv("VELOXSEG_UPCONV_MFMA4"); vx_upconv_mfma4_on = (e && e[0] == '0') ? 0 : 1; }
     return vx_upconv_mfma4_on == 1 && (wd & 3) == 0;
 }
 

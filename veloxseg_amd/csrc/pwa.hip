@@ -1354,8 +1354,7 @@ extern "C" int vx_pwa_scatter_bwd_all_wz(const float* const* douts, float* dtok,
     if (int e = vx_plan_check(plan, "vx_pwa_scatter_bwd_all_w")) return e;
     VX_REQUIRE(douts && dtok && c > 0 && M >= 1 && M <= 4 && B > 0, "vx_pwa_scatter_bwd_all_w: bad args");
     VX_REQUIRE(extra_zero == nullptr || (extra_floats > 0 && extra_floats % 4 == 0 && ((uintptr_t)extra_zero & 15) == 0), "vx_pwa_scatter_bwd_all_wz: the extra buffer must be 16-byte aligned, a multiple of 4 floats");
-    static const int off = getenv("VELOXSEG_SCATTER_BWD_W") && getenv("VELOXSEG_SCATTER_BWD_W")[0] == '0';      // (A/B)
-    if (off || plan->nb > 4 || vx_scatter_bwd_kind(plan, c, B, 0) != 0) return 1;
+    if (plan->nb > 4 || vx_scatter_bwd_kind(plan, c, B, 0) != 0) return 1;
     for (int i = 1; i < plan->nb; ++i) if (vx_scatter_bwd_kind(plan, c, B, i) == 0) return 1;      // (a second identity scale would zero nothing but is not expected: keep the old path)
     VxScPtrs ptrs = {};
     for (int m = 0; m < M; ++m) { VX_REQUIRE(douts[m], "vx_pwa_scatter_bwd_all_w: null gradient %d", m); ptrs.in[m] = douts[m]; }

@@ -831,12 +831,8 @@ extern "C" int vx_ln_pw_bwd(const void* const* ptrs, int M, int NS, const int* J
     return 0;
 }
 
-// tile width of the post kernels: 64 voxels (T = 4) where the grid is large enough to fill the chip with them (VELOXSEG_POST_T4=0: 16-voxel tiles everywhere)
-static int post_tile_t(long V) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("VELOXSEG_POST_T4"); on = (e && atoi(e) == 0) ? 0 : 1; }
-    return on ? pf_tile_t(V) : 1;
-}
+// tile width of the post kernels: 64 voxels (T = 4) where the grid is large enough to fill the chip with them
+static int post_tile_t(long V) { return pf_tile_t(V); }
 static inline size_t post_lds_floats(int T, int NW, int C, int Cv, int R, bool bwd) {
     const size_t S = T == 4 ? 64 : 20, NT = 16 * T, NP = 64 * NW / NT;
     return bwd ? (size_t)(4 * C + R) * S + 2 * NP * NT + 3 * NT + 2 * C + R : (size_t)(Cv + 2 * C + R) * S + NP * NT + 4 * C + R;

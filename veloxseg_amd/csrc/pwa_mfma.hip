@@ -28,7 +28,7 @@ struct VxAttnM {
     int n[3];
     float scale;
     int lin_cst, Tsz;
-    int xcd;       // (round 6) bit 0 / 1: forward / backward blocks of one window are placed on one XCD (vx_xcd_rows); VELOXSEG_ATTN_XCD
+    int xcd;       // (round 6) bit 0 / 1: forward / backward blocks of one window are placed on one XCD (vx_xcd_rows); always 3
 };
 
 // Staging loops: 8 independent loads per thread are issued before the first LDS store (a rolled load -> store loop pays one L2 round trip per
@@ -1216,8 +1216,7 @@ static bool vx_am_fill(VxAttnM& A, const VxPwaPlan* P, int B, int M, int cq) {
     A.scale = 1.0f / sqrtf((float)cq);
     A.lin_cst = ((P->n[0] - 1) * (2 * P->n[1] - 1) + (P->n[1] - 1)) * (2 * P->n[2] - 1) + (P->n[2] - 1);
     A.Tsz = (2 * A.n[0] - 1) * (2 * A.n[1] - 1) * (2 * A.n[2] - 1);
-    static const int xcd = [] { const char* e = getenv("VELOXSEG_ATTN_XCD"); return e ? atoi(e) : 3; }();
-    A.xcd = xcd;
+    A.xcd = 3;
     return true;
 }
 static size_t vx_am_tab_floats(const VxAttnM& A) { return (size_t)((A.l + 3) & ~3) + (size_t)((A.Tsz + 3) & ~3); }
@@ -1342,15 +1341,14 @@ __global__ void __launch_bounds__(256) vx_zero_many_k(VxZeroMany z) {
 // => one-pass for a single modality below 512 tokens.  (Hecktor's 32-token windows -- 64 rows per window at M = 2 -- are faster alone too, but the STEP is not: 1445 vs
 // 1455 patches/s with them on the one-pass kernel, whose blocks hold more LDS beside the other lanes' kernels; BraTS 128^3: 730 -> 748 fp32, 780 -> 821 in the bf16 mode.)
 static bool vx_b1_short(const VxAttnM& A) { return A.M == 1 && A.l < 512; }
-static int g_b1_short = -1;
-static int vx_b1_short_on() { if (g_b1_short < 0) g_b1_short = getenv("VELOXSEG_B1_SHORT") ? atoi(getenv("VELOXSEG_B1_SHORT")) : 1; return g_b1_short; }      // A/B: 0 = the selection of rounds 3 - 5
+static int g_b1_short = 1;
+static int vx_b1_short_on() { return g_b1_short; }      // A/B: 0 = the selection of rounds 3 - 5
 extern "C" int vx_pwa_attn_set_short(int on) { g_b1_short = on ? 1 : 0; return 0; }
-// fewer than 64 blocks with four query tiles per block: split the queries.  M = 2 (A/B experiment, VELOXSEG_B1_FEW=1): 44 -> 32 us alone at the 4^3 level, no change of the
+// fewer than 64 blocks with four query tiles per block: split the queries.  M = 2 (A/B experiment): 44 -> 32 us alone at the 4^3 level, no change of the
 // step (894 vs 895) -> off.  The short-window geometries above: 22 -> 20 us (level 3) and 27 -> 20 us (level 4) at M = 1 -> on.
 static bool vx_b1_few(const VxAttnM& A) {
-    static const int on = getenv("VELOXSEG_B1_FEW") ? atoi(getenv("VELOXSEG_B1_FEW")) : -1;
     const int NT = (A.l + 15) / 16;
-    const bool use = on >= 0 ? on != 0 : (vx_b1_short_on() && vx_b1_short(A) && A.l % 16 == 0);
+    const bool use = vx_b1_short_on() && vx_b1_short(A) && A.l % 16 == 0;
     return use && NT >= 2 && (long)A.BH * A.Nt * ((NT + 3) / 4) * ((NT + 3) / 4) < 64;
 }
 extern "C" int vx_pwa_attn_bwd1_ok(const VxPwaPlan* P, int B, int M, int cq, int cv) {
@@ -1414,11 +1412,10 @@ static size_t vx_b1h_shm(int LP, int Tsz, int win, int c) {
 static size_t vx_b1h_shm(const VxAttnM& A, int c) { return vx_b1h_shm(A.l, A.Tsz, VX_B1_WIN, c); }
 // Ragged windows (l % 64 != 0: the shipped 96^3 / Hecktor geometries) on the same kernel, RAG instance: padded length and the lane groups' bin window (0: does not fit)
 struct VxB1hRag { int LP, win; };
-static int g_b1h_rag = -1;
-extern "C" int vx_pwa_attn_set_f16_bwd_ragged(int on) { g_b1h_rag = on < 0 ? 0 : on; return 0; }      // A/B (tests, probes): ragged windows on the f16-pipe backward -- 0 off, 1 (default; VELOXSEG_F16_BWD_RAGGED) where a window fills >= 3/4 of its 64-token chunks, 2 every ragged length
+static int g_b1h_rag = 1;
+extern "C" int vx_pwa_attn_set_f16_bwd_ragged(int on) { g_b1h_rag = on < 0 ? 0 : on; return 0; }      // A/B (tests, probes): ragged windows on the f16-pipe backward -- 0 off, 1 (default) where a window fills >= 3/4 of its 64-token chunks, 2 every ragged length
 static VxB1hRag vx_b1h_rag(const VxAttnM& A, int c) {
     VxB1hRag r = {0, 0};
-    if (g_b1h_rag < 0) g_b1h_rag = getenv("VELOXSEG_F16_BWD_RAGGED") ? atoi(getenv("VELOXSEG_F16_BWD_RAGGED")) : 1;
     if (!g_b1h_rag || A.l < 8) return r;
     const int LP = (A.l + 63) / 64 * 64;
     // (measured alone, B = 4, M = 2, tools/attn_bwd_probe.py, f16 ragged / fp32 one-pass: l = 216 80 / 108 us; l = 27 92 / 74, l = 32 89 / 72 -- a 64-token chunk that is
@@ -1432,13 +1429,12 @@ static VxB1hRag vx_b1h_rag(const VxAttnM& A, int c) {
     r.LP = LP; r.win = win;
     return r;
 }
-static int g_b1h_m1 = -1;
+static int g_b1h_m1 = 0;
 extern "C" int vx_pwa_attn_set_f16_bwd_m1(int on) { g_b1h_m1 = on < 0 ? 0 : on; return 0; }
 extern "C" int vx_pwa_attn_bwd1h_ok(const VxPwaPlan* P, int B, int M, int cq, int cv) {
     if (!vx_am_f16_bwd || !(vx_am_enabled & 2) || (vx_am_enabled & 4) || P == nullptr || B <= 0 || M < 1 || M > 2) return 0;
     if (!((cq == 4 && cv == 4) || (cq == 8 && cv == 8))) return 0;
-    if (M == 1) {        // (round 6) one modality (BraTS): the MF = 1 instance.  VELOXSEG_F16_BWD_M1=0 / vx_pwa_attn_set_f16_bwd_m1(0): the fp32 kernels (A/B)
-        if (g_b1h_m1 < 0) g_b1h_m1 = getenv("VELOXSEG_F16_BWD_M1") ? atoi(getenv("VELOXSEG_F16_BWD_M1")) : 0;
+    if (M == 1) {        // (round 6) one modality (BraTS): the MF = 1 instance, off by default (the fp32 kernels); vx_pwa_attn_set_f16_bwd_m1(1 | 2) selects it (A/B)
         if (!g_b1h_m1 || (g_b1h_m1 == 2 && P->l < 512)) return 0;
     }
     VxAttnM A;
@@ -1460,8 +1456,6 @@ int vx_pwa_attn_bwd1h(const float* Q, const float* K, const float* V, const floa
     // query splits: as few as fill the chip (every split costs one more float atomic per dK / dV element): >= 4 blocks per CU
     int QS = 1;
     while (QS < nchunk && nwin * nchunk * QS < 4 * 256) QS *= 2;
-    static const int qs_env = getenv("VELOXSEG_F16_BWD_QS") ? atoi(getenv("VELOXSEG_F16_BWD_QS")) : 0;          // (A/B: query splits per window and key chunk; 0 = the rule above)
-    if (qs_env > 0) { QS = qs_env < nchunk ? qs_env : nchunk; while (nchunk % QS) --QS; }
     const dim3 grid((unsigned)(nchunk * QS), (unsigned)nwin);
     const int atomic_dq = nchunk > 1 ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;

@@ -23,22 +23,7 @@ import torch.distributed as dist
 from . import _hip as H
 from . import functional as VF
 
-TAPE_WGRAD_SIDE = os.environ.get("VELOXSEG_TAPE_WGRAD_SIDE", "0") != "0"
-# the flat-gradient fill at the tail of the segmentation decoder's forward lane (default) or at the head of the encoder forward (0; A/B)
-ZERO_GRAD_IN_DEC_FWD = os.environ.get("VELOXSEG_ZERO_GRAD_DEC", "1") != "0"
-# the weight images of the JLC blocks built ahead, on a side lane at the head of the encoder forward (0: in front of every block, A/B)
-WIMG_PREFETCH = os.environ.get("VELOXSEG_WIMG_PREFETCH", "1") != "0"
-# ... and those of the patch-expand heads: OFF.  Same box, with / without: autopet128 +0.1 ... 0.3 %, autopet96 +0.4 %, hecktor +0.6 %, but brats128 fp32 -4 % (755 -> 723 patches/s):
-# its two decoder lanes then reach their 100 us patch-expand kernels at the same moment and the decoder fan takes 576 instead of 458 us although its critical path is 15 us
-# shorter (tools/tape_critical_path.py brats128) -- the two preparation launches had been staggering them.
-EXPAND_PREFETCH = os.environ.get("VELOXSEG_EXPAND_PREFETCH", "0") == "1"
-# TapedPredictor: the weight images of the JLC blocks built once and kept across forwards (0: rebuilt inside every replay, A/B)
-PREDICTOR_KEEP_IMAGES = os.environ.get("VELOXSEG_PREDICTOR_KEEP_IMAGES", "1") != "0"
-TAPE_PGO = os.environ.get("VELOXSEG_TAPE_PGO", "0") == "1"                      # profile-guided lane layout of the encoder tapes (csrc/tape.hip vx_tape_build_pgo)
-TAPE_PGO_STAGES = tuple(k for k in os.environ.get("VELOXSEG_TAPE_PGO_STAGES", "enc_bwd,enc_fwd").split(",") if k)
-TAPE_WGRAD_DEFER = os.environ.get("VELOXSEG_TAPE_WGRAD_DEFER", "1") != "0"      # taped encoder backward: weight gradients at the end of their own stream
-WG_EARLY = os.environ.get("VELOXSEG_WG_EARLY", "1") != "0"      # taped steps: dec_wg[k] queued behind dec_bwd[k] instead of behind the join of the decoder-backward fan
-WGRAD_STREAM = os.environ.get("VELOXSEG_WGRAD_STREAM", "0") != "0"      # experiment (off): weight-gradient kernels deferred to a side stream -- measured 13.5 vs 12.0 ms/step, they steal CUs from the critical path
+TAPE_PGO = False                      # profile-guided lane layout of the encoder tapes (csrc/tape.hip vx_tape_build_pgo); tests set it before the first step captures
 
 
 def _align(n: int, a: int = 64) -> int:
@@ -231,8 +216,6 @@ class TapedPredictor:
         """(round 6) between the forwards of a predictor the weights do not change: the weight images of the JLC blocks the eval forward runs (encoder conv branch, segmentation
         decoder) are built ONCE, before the capture, and kept (functional.jlc_prefetch(keep=True)) -- the tape then holds none of their preparation launches (14 of ~250).
         They are valid while the signature below holds (storage, version counters, the weights epoch a TrainEngine bumps); _vxops drops an entry that is not."""
-        if not PREDICTOR_KEEP_IMAGES:
-            return
         from .model.components.conv_blocks import JLC
         mdl = getattr(self.model, "_model", self.model)        # (utils.inference_runtime.Net wraps the network)
         enc = getattr(mdl, "encoder", None)
@@ -254,7 +237,7 @@ class TapedPredictor:
                 if isinstance(blk, JLC):
                     VF.jlc_prefetch(blk, grid(lvl), cur, keep=True)
         head = getattr(dec, "out_conv1", None)
-        if head is not None:                             # the patch-expand head's forward image too (one decoder: no second lane to collide with, cf. EXPAND_PREFETCH)
+        if head is not None:                             # the patch-expand head's forward image too (one decoder: no second lane to collide with, cf. TrainEngine._prefetch_weight_images)
             VF.expand_prefetch(head[0], cur, keep=True)
 
     def _capture_body(self, x):
@@ -295,11 +278,11 @@ class TapedPredictor:
         if slots is None:
             slots = self._sig_slots = ([(m._parameters, n) for m in self.model.modules() for n, p in m._parameters.items() if p is not None]
                                        + [(m._buffers, n) for m in self.model.modules() for n, b in m._buffers.items() if b is not None])
-        out = [VF.weights_epoch() if PREDICTOR_KEEP_IMAGES else 0]
+        out = [VF.weights_epoch()]
         for d, n in slots:
             t = d.get(n)
             # (_version: an in-place update of a weight -- optimizer.step(), load_state_dict -- invalidates the weight images the tapes were captured without)
-            out.append(None if t is None else (t.data_ptr(), t.dtype, t.device.index, t._version if PREDICTOR_KEEP_IMAGES else 0))
+            out.append(None if t is None else (t.data_ptr(), t.dtype, t.device.index, t._version))
         return tuple(out)
 
     # a tape holds a CUDAGraph and raw handles: copies / pickles of the model carry a FRESH, empty predictor (copy.deepcopy(model) for an EMA copy,
@@ -397,13 +380,13 @@ class TrainEngine:
         # (default) = the decoder bucket during the encoder backward, the encoder's gradients in one bucket after it.  A marker joins every forked
         # stream of the stage: measured on one GPU the markers cost 0.85 ms per step (7.50 vs 6.65 ms), more than the ~0.2 ms of all-reduce
         # (5.5 MB over xGMI) they can hide
-        self.level_buckets = bool(level_buckets) or os.environ.get("VELOXSEG_LEVEL_BUCKETS") == "1"
+        self.level_buckets = bool(level_buckets)
         # Taped steps only: the decoders' weight gradients (a ~1 ms sink on the fourth lane), their all-reduce and the decoder half of AdamW are NOT joined at the end
         # of the step: the next step's encoder forward -- which reads encoder parameters only, and leaves a lane idle -- starts as soon as the encoder half of AdamW is
         # done, and the join moves to just before the next decoder forward.  Same arithmetic, same collectives in the same order; what changes for the caller:
         # after step() returns, work on the CURRENT stream is ordered behind the encoder update only -- read decoder parameters / gradients after flush() (or a
         # device synchronise).  Opt-in (bench.py and the step loop of utils/train_loop.py turn it on).
-        self.pipeline_tail = bool(pipeline_tail) or os.environ.get("VELOXSEG_PIPELINE_TAIL") == "1"
+        self.pipeline_tail = bool(pipeline_tail)
         self._tail_pending = False
         self._two_buckets = bool(use_graph) and replay == "tape" and not self.level_buckets
         if precision not in ("fp32", "bf16"):
@@ -440,10 +423,10 @@ class TrainEngine:
         if self.comm_placement not in ("lane", "fresh_after", "fresh_before"):
             raise ValueError("VELOXSEG_COMM_PLACEMENT must be lane, fresh_after or fresh_before")
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
-        # `dp`: the step issues its collectives.  Normally world > 1; a process group of ONE rank (VELOXSEG_FORCE_COMM=1 / force_comm) runs the same code path -- the
+        # `dp`: the step issues its collectives.  Normally world > 1; a process group of ONE rank (force_comm) runs the same code path -- the
         # all-reduces go through ProcessGroupNCCL's own stream and events for real and change no value -- which is how the RCCL path is exercised and its cost beside
         # the four busy hardware queues measured on a one-GPU box (tests/test_dp_gpu.py, profiles/r05_comm_world1_nccl.json)
-        self.dp = self.world > 1 or ((bool(force_comm) or os.environ.get("VELOXSEG_FORCE_COMM") == "1") and dist.is_available() and dist.is_initialized())
+        self.dp = self.world > 1 or (bool(force_comm) and dist.is_available() and dist.is_initialized())
         self.overlap = overlap and self.dp
         self.use_graph = use_graph
         if replay not in ("tape", "graph"):
@@ -514,19 +497,7 @@ class TrainEngine:
         self.last_outputs = [o.detach() for o in outs]
 
     def _backward(self, loss):
-        """loss.backward() with the weight-gradient kernels of the convolutions on a side stream (csrc/_vxops.cpp WgradSide): only the input
-        gradients stay on the critical path; the launching stream is re-joined before anything reads the parameter gradients"""
-        m = VF.cpp_module() if (WGRAD_STREAM and not self.use_graph) else None
-        if m is None:
-            loss.backward()
-            self._join_side_streams()
-            return
-        m.set_wgrad_stream(True)
-        try:
-            loss.backward()
-        finally:
-            m.set_wgrad_stream(False)
-            m.wgrad_join(torch.cuda.current_stream(self.dev).cuda_stream, self.dev.index or 0, True)
+        loss.backward()
         self._join_side_streams()
 
     def _join_side_streams(self, waiter=None):
@@ -559,9 +530,6 @@ class TrainEngine:
             lo, hi = by_trigger[trigger]
             cur = torch.cuda.current_stream(self.dev)
             self.comm_stream.wait_stream(cur)
-            m = VF.cpp_module() if WGRAD_STREAM else None
-            if m is not None:
-                m.wgrad_join(self.comm_stream.cuda_stream, self.dev.index or 0, False)      # weight gradients deferred to the side stream
             for s_ in VF.all_side_streams(self.dev):      # the weight-gradient kernels ran on the streams of their nodes
                 self.comm_stream.wait_stream(s_)
             with torch.cuda.stream(self.comm_stream):
@@ -609,8 +577,7 @@ class TrainEngine:
     def _s_enc_fwd(self):
         if self._pipe_active():
             self.flat.grad[:self.flat.split].zero_()       # (pipelined tail: the decoder half may still be in use by the previous step's dec_wg / AdamW: zeroed in _s_loss)
-        elif not ZERO_GRAD_IN_DEC_FWD:
-            self.flat.zero_grad()                          # (default: at the end of the segmentation decoder's forward lane, _s_dec_fwd -- off the head of the step's chain)
+        # (otherwise: at the end of the segmentation decoder's forward lane, _s_dec_fwd -- off the head of the step's chain)
         VF.advance_rng(self.dev)
         self._prefetch_weight_images()
         self._drop_level_hooks()
@@ -647,7 +614,7 @@ class TrainEngine:
         return int(getattr(self.model, "n_classes", 0) or self.model.decoder.n_classes)
 
     def _mark_levels(self):
-        return self.use_graph and self.replay_mode == "tape" and ((self.dp and self.overlap and self.level_buckets) or os.environ.get("VELOXSEG_FORCE_MARKERS") == "1")
+        return self.use_graph and self.replay_mode == "tape" and self.dp and self.overlap and self.level_buckets
 
     def _drop_level_hooks(self):
         for h in getattr(self, "_level_hooks", []):
@@ -663,7 +630,7 @@ class TrainEngine:
             # the weight-gradient launches of this level are deferred closures (set_wgrad_defer in _s_enc_bwd): launch them NOW, each on the stream it
             # was queued from, so that the marker -- and with it the all-reduce of this level's bucket -- is ordered after them.  Without this the
             # bucket was reduced before its deferred weight gradients ran and they landed on top of the reduced values (ranks diverge).
-            m.wgrad_join(st.cuda_stream, self.dev.index or 0, True)
+            m.wgrad_join(st.cuda_stream, self.dev.index or 0)
         with torch.cuda.stream(st):
             capturing = torch.cuda.is_current_stream_capturing()
         for s_ in VF.all_side_streams(self.dev):
@@ -705,7 +672,7 @@ class TrainEngine:
                 bl.seg_forward([t.detach() for t in self._outs[0][:-1]], self.labels)
             else:
                 self._rc_c[k] = bl.rc_forward(self._outs[k][0].detach(), self.x, self._ch_off[k - 1])
-        if k == 0 and ZERO_GRAD_IN_DEC_FWD and not self._pipe_active():
+        if k == 0 and not self._pipe_active():
             # (round 6) the flat gradient is zeroed HERE, at the tail of the segmentation decoder's forward lane (the shortest of the fan: 439 / 452 / 451 us), instead of at the
             # head of the encoder forward: nothing accumulates into it before the backward stages, and the 9 MB fill leaves the step's critical chain
             self.flat.zero_grad()
@@ -714,7 +681,7 @@ class TrainEngine:
         """(round 6) the weight images of every JLC block of the step -- functions of the weights alone -- are built at the head of the encoder forward on a side lane, in the
         order the blocks need them (encoder levels 1..4, then every decoder's levels 3, 2, 1), instead of in front of each block's convolutions on the forward chains
         (two or three 6 us launches per block: functional.jlc_prefetch).  The decoders' images are ready long before the decoder fan starts (the stage joins its side streams)."""
-        if not WIMG_PREFETCH or self._pipe_active():
+        if self._pipe_active():
             return
         from .model.components.conv_blocks import JLC
         enc = getattr(self.model, "encoder", None)
@@ -734,10 +701,9 @@ class TrainEngine:
         cur = torch.cuda.current_stream(self.dev)
         side.wait_stream(cur)
         self._pf_blocks = [blk for blk, g in todo if VF.jlc_prefetch(blk, g, side)]
-        for d in (decs if EXPAND_PREFETCH else []):      # the patch-expand heads (out_conv / out_conv1: 3^3 conv + PixelShuffle): forward and input-gradient images
-            head = getattr(d, "out_conv1", None) or getattr(d, "out_conv", None)
-            if head is not None:
-                VF.expand_prefetch(head[0], side)
+        # (not the images of the patch-expand heads: autopet128 +0.1 ... 0.3 %, autopet96 +0.4 %, hecktor +0.6 %, but brats128 fp32 -4 % (755 -> 723 patches/s): its two decoder
+        # lanes then reach their 100 us patch-expand kernels at the same moment and the decoder fan takes 576 instead of 458 us although its critical path is 15 us shorter
+        # (tools/tape_critical_path.py brats128) -- the two preparation launches had been staggering them)
 
     def _prefetch_settle(self):
         """after the encoder-forward stage has joined its side streams: the decoders' blocks need not wait for an event of another stage; entries nobody took are dropped"""
@@ -773,28 +739,12 @@ class TrainEngine:
         from .utils.loss import Loss
         self._bl = None
         ok = (self.use_graph and self.replay_mode == "tape" and isinstance(self.criterion, Loss) and hasattr(self.model, "decode_branch")
-              and self.model.num_modalities >= 1 and os.environ.get("VELOXSEG_STAGED_LOSS", "1") != "0")
+              and self.model.num_modalities >= 1)
         if ok:
             in_ch = list(self.model.encoder.in_channels)
             self._ch_off = [sum(in_ch[:m]) for m in range(len(in_ch))]
             self._n_heads = None
             self._bl = "pending"            # built at the first enc_fwd, when the number of heads is known from the decoder outputs
-
-    @contextlib.contextmanager
-    def _wgrad_side(self):
-        """Inside a taped stage the weight-gradient kernels can go to a side stream (csrc/_vxops.cpp WgradSide): in the captured DAG they become a
-        branch of their own instead of links of the input-gradient chain.  Off by default (VELOXSEG_TAPE_WGRAD_SIDE): the critical path gets
-        0.3 ms shorter and the step slower -- the big weight-gradient grids then take CUs from the chain."""
-        m = VF.cpp_module() if (self.use_graph and self.replay_mode == "tape" and TAPE_WGRAD_SIDE) else None
-        if m is None:
-            yield
-            return
-        m.set_wgrad_stream(True)
-        try:
-            yield
-        finally:
-            m.set_wgrad_stream(False)
-            m.wgrad_join(torch.cuda.current_stream(self.dev).cuda_stream, self.dev.index or 0, True)
 
     def _s_loss(self):
         if self._pipe_active():
@@ -810,15 +760,14 @@ class TrainEngine:
         outs_d = [[o.detach().requires_grad_(True) for o in outs] for outs in self._outs]
         self.last_outputs = self.model.assemble_train(outs_d)      # detached leaves: what the per-step metrics read
         loss = self.criterion(self.last_outputs, self.labels, sr_labels=self.x)
-        with self._wgrad_side():
-            loss.backward()
+        loss.backward()
         self._douts = [[o.grad for o in od] for od in outs_d]
         torch.add(loss.detach(), 0.0, out=self.loss)      # a kernel, not hipMemcpyAsync: memcpy nodes cannot be read back into a launch tape
 
     def _split_dec_wgrad(self):
         """taped steps: the weight-gradient kernels of a decoder's backward become a tape of their own (dec_wg[k]) that is replayed on the lane the
         encoder backward leaves idle, concurrently with it -- the decoder fans then only carry the input-gradient chains"""
-        return self.use_graph and self.replay_mode == "tape" and TAPE_WGRAD_DEFER and VF.cpp_module() is not None
+        return self.use_graph and self.replay_mode == "tape" and VF.cpp_module() is not None
 
     def _s_dec_bwd(self, k):
         m = VF.cpp_module() if self._split_dec_wgrad() else None
@@ -835,7 +784,7 @@ class TrainEngine:
         m = VF.cpp_module()
         m.set_wgrad_defer(True)
         try:
-            m.wgrad_join(torch.cuda.current_stream(self.dev).cuda_stream, self.dev.index or 0, True)
+            m.wgrad_join(torch.cuda.current_stream(self.dev).cuda_stream, self.dev.index or 0)
         finally:
             m.set_wgrad_defer(False)
 
@@ -844,12 +793,10 @@ class TrainEngine:
         if bl is not None:        # this branch's share of the loss backward, then its decoder
             outs = self._outs[k]
             grads = (bl.seg_backward() + [bl.dgs]) if k == 0 else [bl.rc_backward(self._rc_c[k], self.x, self._ch_off[k - 1]), bl.dgm[k - 1]]
-            with self._wgrad_side():
-                torch.autograd.backward(list(outs), grads)
+            torch.autograd.backward(list(outs), grads)
             return
         pairs = [(o, g) for o, g in zip(self._outs[k], self._douts[k]) if g is not None]
-        with self._wgrad_side():
-            torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
+        torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
 
     def _s_enc_bwd(self):
         bt, groups = [], []
@@ -860,21 +807,20 @@ class TrainEngine:
                 groups.append(gs)
         bg = self._sum_groups(groups)
         self._stage_stream = torch.cuda.current_stream(self.dev)
-        # taped encoder backward: the weight-gradient kernels are deferred to the end of the stream they were queued on (csrc/_vxops.cpp WgradSide,
-        # `same`): the mixer / level-input gradients that the OTHER lanes wait for leave the conv chain before its weight gradients run
-        m = VF.cpp_module() if (self.use_graph and self.replay_mode == "tape" and TAPE_WGRAD_DEFER) else None
+        # taped encoder backward: the weight-gradient kernels are deferred to the end of the stream they were queued on (csrc/_vxops.cpp WgradQueue):
+        # the mixer / level-input gradients that the OTHER lanes wait for leave the conv chain before its weight gradients run
+        m = VF.cpp_module() if (self.use_graph and self.replay_mode == "tape") else None
         if m is not None:
             m.set_wgrad_defer(True)
         self._enc_bwd_defer = m is not None
         try:
-            with self._wgrad_side():
-                torch.autograd.backward(bt, bg)
+            torch.autograd.backward(bt, bg)
         finally:
             self._enc_bwd_defer = False
             if m is not None:
-                # (VELOXSEG_WGRAD_SPREAD=3 deals these sinks onto the stage's three lanes instead of the stream they were queued from: measured 7.21 vs
-                # 6.28 ms per step on one MI355X -- the big weight-gradient grids then land beside the tail of the chain; off)
-                m.wgrad_join(self._stage_stream.cuda_stream, self.dev.index or 0, True, int(os.environ.get("VELOXSEG_WGRAD_SPREAD", "0")))
+                # (dealing these sinks onto the stage's three lanes instead of the stream they were queued from measured 7.21 vs 6.28 ms per step on one
+                # MI355X -- the big weight-gradient grids then land beside the tail of the chain)
+                m.wgrad_join(self._stage_stream.cuda_stream, self.dev.index or 0)
                 m.set_wgrad_defer(False)
             self._drop_level_hooks()
 
@@ -1050,8 +996,6 @@ class TrainEngine:
         """Run `fn` with a trivial side-stream branch alive around it, so that every captured graph has more than one branch.
         ROCm 7.2 replays single-branch graphs through a batched AQL-packet path that intermittently corrupts this step after a
         device synchronise (veloxseg_amd/__init__.py); multi-branch graphs take the ordinary per-node path."""
-        if os.environ.get("VX_NO_FORK") == "1":         # debugging only (tools/graph_replay_repro.py)
-            return fn(*args)
         cur = torch.cuda.current_stream(self.dev)
         self._fork_stream.wait_stream(cur)
         with torch.cuda.stream(self._fork_stream):
@@ -1064,7 +1008,7 @@ class TrainEngine:
         g = torch.cuda.CUDAGraph(keep_graph=True) if tape else torch.cuda.CUDAGraph()
         # with RCCL running (world > 1) its watchdog thread polls events while we capture: in the default "global" error mode that invalidates the
         # capture; "thread_local" checks only the capturing thread (kernels queued by autograd's device thread are captured either way)
-        mode = "thread_local" if (self.dp or os.environ.get("VELOXSEG_CAPTURE_MODE") == "thread_local") else "global"
+        mode = "thread_local" if self.dp else "global"
         with warnings.catch_warnings(record=True) as caught:
             warnings.simplefilter("always")
             with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
@@ -1125,7 +1069,7 @@ class TrainEngine:
             rng.copy_(rng0)
             self._replay(comm=False)
             torch.cuda.synchronize()
-            for key in TAPE_PGO_STAGES:
+            for key in ("enc_bwd", "enc_fwd"):
                 t = G.get(key)
                 if isinstance(t, LaunchTape):
                     t.relayout(3 if (key == "enc_bwd" and "dec_wg" in G) else self.tape_lanes)
@@ -1202,7 +1146,7 @@ class TrainEngine:
             self._last_outputs = None          # the replay rewrote the parts: last_outputs assembles them again instead of returning an earlier step's concatenation
         split, n = self.flat.split, self.flat.numel
         wg_lane = None
-        if "dec_wg" in G and self.replay_mode == "tape" and WG_EARLY and len(G["dec_bwd"]) <= 3:
+        if "dec_wg" in G and len(G["dec_bwd"]) <= 3:
             # The decoders' weight gradients run one after the other on the fourth lane, beside the encoder backward on the other three.  dec_wg[k] needs dec_bwd[k]
             # only, and the fourth lane is idle during the decoder-backward fan: each dec_wg[k] is queued behind ITS decoder's backward (a hop from that lane), the
             # decoders that finish first (the reconstruction branches: shorter tapes) first -- the weight gradients start while the longest decoder is still in its

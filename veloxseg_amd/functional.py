@@ -22,19 +22,18 @@ WGRAD_ENTRY = "vx_conv3d_bwd_weight_tiled"    # "vx_conv3d_bwd_weight" = untiled
 USE_EXPAND_MFMA = True                        # patch-expand input gradient on fp32 MFMA (False = conv_s1 VALU kernel)
 # fp32 mode of the patch-expand layers (forward + input gradient, 49 % of the training FLOPs): 3 = every fp32 operand as three bf16 pieces, six bf16 MFMAs per
 # pair (the fp32 product to 2^-27; 2.7 x fewer matrix-pipe clocks than v_mfma_f32_16x16x4_f32), 2 = two pieces / three MFMAs (~1e-5 relative), 0 = fp32 MFMA
-EXPAND_SPLIT = int(os.environ.get("VELOXSEG_EXPAND_SPLIT", "22"))      # 22 = two scaled fp16 pieces (3 MFMAs per product, closer to fp64 than 3 bf16 pieces); 3 / 2 = bf16 pieces; 0 = fp32 MFMA
+EXPAND_SPLIT = 22      # 22 = two scaled fp16 pieces (3 MFMAs per product, closer to fp64 than 3 bf16 pieces); 3 / 2 = bf16 pieces; 0 = fp32 MFMA
 USE_S1 = True                                 # register-blocked stride-1 conv kernel (False = generic kernels, for A/B tests)
 USE_IN_ROW = True                             # InstanceNorm of short rows (V <= 4096): statistics + application in one launch
 IN_ROW_MAX = 4096
-USE_WGRAD_WS = os.environ.get("VELOXSEG_WGRAD_WS", "0") != "0"   # tiled weight gradient through a partial-sum workspace (deterministic order) instead of float atomics (30 fewer launches per step: +2 %)
+USE_WGRAD_WS = False                          # tiled weight gradient through a partial-sum workspace (deterministic order) instead of float atomics (30 fewer launches per step: +2 %)
 _wgrad_ws = {}
 USE_PATCHIFY = True                           # kernel == stride convs (PatchEmbed) as patchify + 1x1 conv (False = generic direct conv)
 USE_LOSS_BWD4 = True                          # loss backward of all deep-supervision heads in one launch (False = one launch per head)
-USE_DOWN_MFMA = os.environ.get("VELOXSEG_DOWN_MFMA", "1") != "0"   # MFMA weight gradient of the k7 s4 p3 stem conv (False = tiled VALU kernel)
 USE_GCONV1 = True                             # dedicated weight-gradient kernel of the 1x1x1 grouped JLC conv (False = tiled kernel)
-PW_MFMA_MAX_V = int(os.environ.get("VELOXSEG_PW_MFMA_MAX_V", "4096"))   # 1x1 convs on volumes up to this many voxels use the MFMA tile kernel
+PW_MFMA_MAX_V = 4096                          # 1x1 convs on volumes up to this many voxels use the MFMA tile kernel
 BRANCH_STREAMS = True                         # independent sub-networks (M+1 decoders; encoder conv chain vs PWA chain) run on forked HIP streams
-MODALITY_STREAMS = int(os.environ.get("VELOXSEG_MODALITY_STREAMS", "1"))   # 1: per-modality halves of a PWA block on forked streams; 2: + PatchEmbed / PatchMerging
+MODALITY_STREAMS = 1                          # 1: per-modality halves of a PWA block on forked streams; 2: + PatchEmbed / PatchMerging
 IN_EPS = 1e-5      # nn.InstanceNorm3d default (reference common_function.py:63-66)
 LN_EPS = 1e-6      # reference attention_utils.py:15
 
@@ -217,11 +216,8 @@ def cpp_module(reload: bool = False):
             try:
                 H.LIB.load()
                 from . import _vxops
-                _vxops.set_fuse_gelu(os.environ.get("VELOXSEG_FUSE_GELU", "1") != "0")
-                _vxops.set_down_mfma(USE_DOWN_MFMA)
                 _vxops.set_expand_split(EXPAND_SPLIT)
                 _vxops.set_tile_min_c(TILE_MIN_C)
-                _vxops.set_fuse_pw_bwd(os.environ.get("VELOXSEG_FUSE_PW_BWD", "1") != "0")
                 _vxops.set_flags(USE_S1, USE_EXPAND_MFMA, USE_GCONV1, USE_WGRAD_WS, USE_PATCHIFY, USE_IN_ROW, PW_MFMA_MAX_V, IN_ROW_MAX, IN_EPS, LN_EPS)
                 _CPP[1] = _vxops
             except ImportError as e:
@@ -234,7 +230,7 @@ def cpp_module(reload: bool = False):
 
 
 _PRECISION = "fp32"
-BF16_STORAGE = os.environ.get("VELOXSEG_BF16_STORAGE", "1") != "0"
+BF16_STORAGE = os.environ.get("VELOXSEG_BF16_STORAGE", "1") != "0"      # (tests assign it as well)
 
 
 def set_precision(mode: str):
@@ -255,10 +251,10 @@ def set_precision(mode: str):
     # flat gradients, AdamW, every block-boundary tensor
     m.set_act_bf16(mode == "bf16" and BF16_STORAGE)
     # the stem DownConv (k7 s4, conv_blocks.py:4-21) on plain fp16 operands in the bf16 mode (one MFMA per step instead of three, half the LDS)
-    H.call("vx_conv_mfma_set_stem_pieces", 1 if (mode == "bf16" and os.environ.get("VELOXSEG_BF16_STEM", "1") != "0") else 2)
+    H.call("vx_conv_mfma_set_stem_pieces", 1 if mode == "bf16" else 2)
     # the JLC grouped convolutions and their weight gradients on the matrix pipe (csrc/jlc_mfma.hip): 3 bf16 pieces per operand (six piece products = the fp32
     # product) in the fp32 mode, ONE piece (plain bf16 operands, fp32 accumulation) in the bf16 mode
-    H.call("vx_jlc_tz_set_pieces", 1 if mode == "bf16" else int(os.environ.get("VELOXSEG_TZ_PIECES", "22")))     # 22 = two scaled fp16 pieces (22 significant bits, three piece products: csrc/jlc_mfma.hip); 3 = three bf16 pieces (A/B)
+    H.call("vx_jlc_tz_set_pieces", 1 if mode == "bf16" else 22)     # 22 = two scaled fp16 pieces (22 significant bits, three piece products: csrc/jlc_mfma.hip)
     _PRECISION = mode
 
 
@@ -270,23 +266,9 @@ def _flag_tuple():
     return (WGRAD_ENTRY, USE_S1, USE_EXPAND_MFMA, USE_GCONV1, USE_WGRAD_WS, USE_PATCHIFY, USE_IN_ROW, PW_MFMA_MAX_V, IN_ROW_MAX)
 
 
-_CPP_OPS = set(os.environ.get("VELOXSEG_CPP_OPS", "conv,in,ln,gelu,axpy,jlc,ffn,pwa,small").split(","))      # debugging: which operators may take the C++ path
-
-
-def _cpp_op(name):
-    return _cpp() if name in _CPP_OPS else None
-
-
-USE_CPP_NODES = os.environ.get("VELOXSEG_CPP_NODES", "1") != "0"      # single operators as C++ autograd nodes (no interpreter in forward or backward)
-
-
-def _cpp_node(name):
-    return _cpp_op(name) if USE_CPP_NODES else None
-
-
 def cpp_node(name):
     """the C++ module when single operators may run as C++ autograd nodes (model code that builds multi-operator nodes asks here), else None"""
-    return _cpp_node(name)
+    return _cpp()
 
 
 def rs_ptr(device, p):
@@ -336,7 +318,7 @@ def _check(x: torch.Tensor, what: str):
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, x2, w, b, K, S, P, G, ps):
-        m = _cpp_op("conv") if x.is_cuda else None
+        m = _cpp() if x.is_cuda else None
         ctx.cst = None
         if m is not None:
             y, ctx.cst = m.conv_fwd(x, x2, w, b, K, S, P, G, ps, H.stream_ptr())
@@ -436,7 +418,7 @@ class _Conv3dFn(torch.autograd.Function):
             elif ctx.s1 and ps == 4 and K == 3 and Cin == 16 and G == 1 and USE_EXPAND_MFMA:
                 xcl = torch.empty((B * D * Hh * W * 16,), device=x.device, dtype=torch.float32)
                 H.call("vx_expand_wgrad_mfma", H.P(x), H.P(xcl), H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cout // 64, D, Hh, W, st)
-            elif (USE_DOWN_MFMA and K == 7 and S == 4 and P == 3 and G == 1 and ps == 1 and x2 is None
+            elif (K == 7 and S == 4 and P == 3 and G == 1 and ps == 1 and x2 is None
                   and H.query("vx_down_wgrad_ws_floats", B, Cin, D, Hh, W, Cout) > 0):
                 nws = H.query("vx_down_wgrad_ws_floats", B, Cin, D, Hh, W, Cout)
                 ws = torch.empty((nws,), device=x.device, dtype=torch.float32)
@@ -459,21 +441,16 @@ class _Conv3dFn(torch.autograd.Function):
 
 # The model reaches the seven C++-registered operators THROUGH THE DISPATCHER (torch.ops.veloxseg.*: Autograd / CUDA / Meta keys registered by csrc/_vxops.cpp) wherever
 # the call has the schema's form; forms the schemas do not carry (two-pointer concat input, the "feeds an InstanceNorm" hint) call the node directly.  A taped step
-# replays captured launches, so the extra dispatcher hop costs the eager path only.  VELOXSEG_DISPATCH=0: always the direct call (A/B).
-USE_DISPATCH = os.environ.get("VELOXSEG_DISPATCH", "1") != "0"
-
-
-def _ops():
-    return torch.ops.veloxseg if (USE_DISPATCH and _cpp_node("conv") is not None) else None
+# replays captured launches, so the extra dispatcher hop costs the eager path only.
 
 
 def conv3d(x, w, b=None, *, x2=None, stride=1, padding=0, groups=1, pixel_shuffle=1, out_bf16=False):
     """Conv3d (+ optional channel-concat input, + optional PixelShuffle store).  out_bf16 (bf16 storage mode, patch-expand layers only): the output is a bfloat16 tensor
     -- the full-resolution logits / reconstructions -- and the backward accepts a bfloat16 gradient; ignored wherever the 16-bit kernels do not apply."""
-    m = _cpp_node("conv") if x.is_cuda else None
+    m = _cpp() if x.is_cuda else None
     if out_bf16 and m is not None and x2 is None and _PRECISION == "bf16" and BF16_STORAGE:
         return m.conv_h(x, w, b, int(w.shape[2]), int(stride), int(padding), int(groups), int(pixel_shuffle))
-    if m is not None and x2 is None and USE_DISPATCH:
+    if m is not None and x2 is None:
         return torch.ops.veloxseg.conv3d(x, w, b, int(stride), int(padding), int(groups), int(pixel_shuffle))
     if m is not None:
         return m.conv(x, x2, w, b, int(w.shape[2]), int(stride), int(padding), int(groups), int(pixel_shuffle))
@@ -517,8 +494,8 @@ class _ConvTransposeK2S2Fn(torch.autograd.Function):
 
 def conv_transpose_k2s2(x, w, b, feeds_instnorm: bool = False):
     """feeds_instnorm: the output goes straight into an InstanceNorm (UpConv): the bias gradient is zero by construction and is not computed"""
-    m = _cpp_node("small") if x.is_cuda else None
-    if m is not None and not feeds_instnorm and b is not None and USE_DISPATCH:
+    m = _cpp() if x.is_cuda else None
+    if m is not None and not feeds_instnorm and b is not None:
         return torch.ops.veloxseg.conv_transpose_k2s2(x, w, b)
     if m is not None:
         return m.upconv_k2s2(x, w, b, bool(feeds_instnorm))
@@ -531,7 +508,7 @@ def conv_transpose_k2s2(x, w, b, feeds_instnorm: bool = False):
 class _InstNormSumFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, res, act, *ys):
-        m = _cpp_op("in") if ys[0].is_cuda else None
+        m = _cpp() if ys[0].is_cuda else None
         ctx.cst = None
         if m is not None:
             out, ctx.cst = m.in_fwd(res, bool(act), list(ys), H.stream_ptr())
@@ -600,11 +577,9 @@ class _InstNormSumFn(torch.autograd.Function):
 
 def instnorm_sum(ys: Sequence[torch.Tensor], act: bool = False, res: Optional[torch.Tensor] = None):
     """(res) + sum_k act(InstanceNorm(y_k))."""
-    m = _cpp_node("in") if ys[0].is_cuda else None
-    if m is not None and 1 <= len(ys) <= 3 and USE_DISPATCH:
-        return torch.ops.veloxseg.instance_norm_sum(list(ys), bool(act), res)
+    m = _cpp() if ys[0].is_cuda else None
     if m is not None and 1 <= len(ys) <= 3:
-        return m.instnorm(res, bool(act), ys[0], ys[1] if len(ys) > 1 else None, ys[2] if len(ys) > 2 else None)
+        return torch.ops.veloxseg.instance_norm_sum(list(ys), bool(act), res)
     return _InstNormSumFn.apply(res, bool(act), *ys)
 
 
@@ -614,7 +589,7 @@ def instnorm_sum(ys: Sequence[torch.Tensor], act: bool = False, res: Optional[to
 class _LayerNormCFFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta):
-        m = _cpp_op("ln") if x.is_cuda else None
+        m = _cpp() if x.is_cuda else None
         ctx.cst = None
         if m is not None:
             out, ctx.cst = m.ln_fwd(x, gamma, beta, H.stream_ptr())
@@ -646,11 +621,9 @@ class _LayerNormCFFn(torch.autograd.Function):
 
 
 def layernorm_cf(x, gamma, beta):
-    m = _cpp_node("ln") if x.is_cuda else None
-    if m is not None and USE_DISPATCH:
-        return torch.ops.veloxseg.layer_norm_cf(x, gamma, beta)
+    m = _cpp() if x.is_cuda else None
     if m is not None:
-        return m.layernorm(x, gamma, beta)
+        return torch.ops.veloxseg.layer_norm_cf(x, gamma, beta)
     return _LayerNormCFFn.apply(x, gamma, beta)
 
 
@@ -660,7 +633,7 @@ def layernorm_cf(x, gamma, beta):
 class _GeluDropFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, p, site):
-        m = _cpp_op("gelu") if a.is_cuda else None
+        m = _cpp() if a.is_cuda else None
         ctx.cst = None
         if m is not None:
             h, ctx.cst = m.gelu_fwd(a, float(p), int(site), _rs_ptr(a.device, p), H.stream_ptr())
@@ -689,7 +662,7 @@ class _GeluDropFn(torch.autograd.Function):
 
 
 def gelu_dropout(a, p: float = 0.0, site: int = 0):
-    m = _cpp_node("gelu") if a.is_cuda else None
+    m = _cpp() if a.is_cuda else None
     if m is not None:
         return m.gelu(a, float(p), int(site), _rs_ptr(a.device, p))
     return _GeluDropFn.apply(a, float(p), int(site))
@@ -700,7 +673,7 @@ class _AxpyDropFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, z, alpha, p, site):
-        m = _cpp_op("axpy") if z.is_cuda else None
+        m = _cpp() if z.is_cuda else None
         ctx.cst = None
         if m is not None:
             out, ctx.cst = m.axpy_fwd(x, z, float(alpha), float(p), int(site), _rs_ptr(z.device, p), H.stream_ptr())
@@ -735,7 +708,7 @@ class _AxpyDropFn(torch.autograd.Function):
 
 
 def residual_dropout(x, z, alpha: float = 1.0, p: float = 0.0, site: int = 0):
-    m = _cpp_node("axpy") if z.is_cuda else None
+    m = _cpp() if z.is_cuda else None
     if m is not None:
         return m.axpy(x, z, float(alpha), float(p), int(site), _rs_ptr(z.device, p))
     return _AxpyDropFn.apply(x, z, float(alpha), float(p), int(site))
@@ -792,7 +765,7 @@ class _JLCFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, mod, p, site):
-        m = _cpp_op("jlc") if x.is_cuda else None
+        m = _cpp() if x.is_cuda else None
         ctx.cst = None
         if m is not None:
             convs = [seq[0] for seq in mod.spatial_convs]
@@ -867,7 +840,7 @@ def jlc_prefetch(mod, grid, stream, keep: bool = False) -> bool:
     """Build the weight images of JLC block `mod` (its next forward runs on a `grid` = (D, H, W) volume) on `stream`, ahead of the block: the block's forward then launches
     no preparation kernels (csrc/_vxops.cpp jlc_prep_into / jlc_fwd_f).  The image buffer is the block's own and is re-used every step; an event recorded on `stream` is left
     on the block and waited for by its forward.  Returns False where the block builds nothing ahead (VALU convolutions, python bindings)."""
-    m = _cpp_node("jlc")
+    m = _cpp()
     if m is None or len(mod.spatial_convs) != 3 or not hasattr(m, "jlc_prep_into"):
         return False
     convs = [seq[0] for seq in mod.spatial_convs]
@@ -895,7 +868,7 @@ def expand_prefetch(conv, stream, keep: bool = False) -> bool:
     """Both weight images of a patch-expand layer (`conv`: the 3^3 convolution in front of PixelShuffle(4)) built on `stream` ahead of its forward (fp16-piece mode;
     csrc/_vxops.cpp expand_prep_into): the layer's forward and input gradient then launch their matrix kernels only.  The buffers are the layer's own, re-used every step.
     The caller joins `stream` before the layer runs (the engine's encoder-forward stage does)."""
-    m = _cpp_node("conv")
+    m = _cpp()
     w = conv.weight
     if m is None or not hasattr(m, "expand_prep_into") or not w.is_cuda or w.dim() != 5:
         return False
@@ -910,7 +883,7 @@ def expand_prefetch(conv, stream, keep: bool = False) -> bool:
 
 
 def jlc_block(x, mod, p: float, site: int):
-    m = _cpp_node("jlc") if x.is_cuda else None
+    m = _cpp() if x.is_cuda else None
     ev = mod.__dict__.pop("_pf_ev", None)                      # images prepared ahead on a side stream (jlc_prefetch): this stream waits for them
     if ev is not None:
         torch.cuda.current_stream(x.device).wait_event(ev)
@@ -928,7 +901,7 @@ class _FFNTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, norm, ffn, p):
-        m = _cpp_op("ffn") if y.is_cuda else None
+        m = _cpp() if y.is_cuda else None
         ctx.cst = None
         if m is not None:
             out, ctx.cst = m.ffn_fwd(y, norm.weight, norm.bias, ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight, ffn.linear2.bias, float(p),
@@ -965,7 +938,7 @@ class _FFNTailFn(torch.autograd.Function):
 
 
 def ffn_tail(y, norm, ffn, p: float):
-    m = _cpp_node("ffn") if y.is_cuda else None
+    m = _cpp() if y.is_cuda else None
     if m is not None:                                          # the whole tail as one C++ autograd node
         return m.ffn(y, norm.weight, norm.bias, ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight, ffn.linear2.bias, float(p), int(ffn.site1), int(ffn.site2),
                      _rs_ptr(y.device, p))
@@ -978,8 +951,8 @@ def ffn_tail(y, norm, ffn, p: float):
 # channel stages (FFN tail of a PWA block, channel MLP of a JLC block) with >= this many channels run on the tile-GEMM chains of csrc/pwa_fused.hip (pwa_post / inmlp +
 # grouped weight gradients) even where csrc/mlp.hip has an instance: at C = 32 (16^3 grids) mlp.hip's per-block weight staging and in-kernel weight-gradient
 # flush cost 45-90 us per launch for 0.5 GFLOP; the tile kernels take 15-25 us (autopet128 747 -> 756 patches/s, autopet96 1061 -> 1079)
-TILE_MIN_C = int(os.environ.get("VELOXSEG_TILE_MIN_C", "32"))
-USE_PWA_FUSED = os.environ.get("VELOXSEG_PWA_FUSED", "1") != "0"      # A/B: 0 = LN, q / k / v, mix, FFN as separate launches per modality
+TILE_MIN_C = 32
+USE_PWA_FUSED = True      # A/B (tests): False = LN, q / k / v, mix, FFN as separate launches per modality
 
 
 def _ptrs(vals):
@@ -988,7 +961,7 @@ def _ptrs(vals):
 
 
 def _submit_wgrad(fn):
-    """run fn(stream_ptr) now on the current stream, or -- while the engine defers weight gradients (csrc/_vxops.cpp WgradSide) -- queue it with the
+    """run fn(stream_ptr) now on the current stream, or -- while the engine defers weight gradients (csrc/_vxops.cpp WgradQueue) -- queue it with the
     other weight-gradient launches of the pass; fn owns its operands"""
     m = _cpp_mod()
     st = H.stream_ptr()
@@ -1140,9 +1113,6 @@ def pwa_pre(xs, norms, projs):
     return [list(out[3 * m: 3 * m + 3]) for m in range(M)], list(out[3 * M:])
 
 
-FAN_OUT = os.environ.get("VELOXSEG_FAN_OUT", "1") != "0"      # A/B: 0 = autograd sums the gradients of a tensor with several consumers itself (one aten add per extra consumer)
-
-
 class _FanOutFn(torch.autograd.Function):
     """n aliases of every tensor of a list, one per consumer.  Backward: the n gradients of every tensor are summed in ONE launch for the whole list (vx_add_many)
     instead of n - 1 aten `add`s per tensor that the autograd engine would issue one by one as the consumers' gradients arrive (6.5 us each on the critical path of
@@ -1189,7 +1159,7 @@ class _FanOutFn(torch.autograd.Function):
 def fan_out(xs, n):
     """[x0, x1, ...] -> [[n aliases of x0], [n aliases of x1], ...] whose gradients meet in one launch (training, CUDA tensors that require grad); else n references"""
     xs = list(xs)
-    if not (FAN_OUT and n >= 2 and xs and torch.is_grad_enabled() and all(x.is_cuda and x.requires_grad for x in xs)):
+    if not (n >= 2 and xs and torch.is_grad_enabled() and all(x.is_cuda and x.requires_grad for x in xs)):
         return [[x] * n for x in xs]
     al = _FanOutFn.apply(n, *xs)
     return [list(al[i * n:(i + 1) * n]) for i in range(len(xs))]
@@ -1302,9 +1272,9 @@ class _SpaceToDepth2Fn(torch.autograd.Function):
 
 
 def space_to_depth2(x):
-    m = _cpp_node("small") if x.is_cuda else None
+    m = _cpp() if x.is_cuda else None
     if m is not None:
-        return torch.ops.veloxseg.space_to_depth2(x) if USE_DISPATCH else m.space_to_depth2(x)
+        return torch.ops.veloxseg.space_to_depth2(x)
     return _SpaceToDepth2Fn.apply(x)
 
 
@@ -1385,7 +1355,7 @@ class _PwaCoreFn(torch.autograd.Function):
 
 def pwa_core(table, plan, cq, cv, qkv: Sequence[torch.Tensor], p_attn: float = 0.0, site: int = 0) -> List[torch.Tensor]:
     M = len(qkv) // 3
-    m = _cpp_node("pwa") if qkv[0].is_cuda else None
+    m = _cpp() if qkv[0].is_cuda else None
     if m is not None and M <= 4:             # the whole core as one C++ autograd node (same C-ABI calls as the python node below)
         return list(m.pwa_core(table, H.ctypes.addressof(plan), int(cq), int(cv), float(p_attn), int(site), _rs_ptr(qkv[0].device, p_attn), list(qkv)))
     return list(_PwaCoreFn.apply(table, plan, int(cq), int(cv), M, float(p_attn), int(site), *qkv))
@@ -1420,9 +1390,9 @@ def upsample_trilinear(x, size):
     size = tuple(int(s) for s in size)
     if tuple(x.shape[2:]) == size:
         return x        # F.interpolate to the same size with align_corners=True is the identity (VeloxSeg.py:183)
-    m = _cpp_node("small") if x.is_cuda else None
+    m = _cpp() if x.is_cuda else None
     if m is not None:
-        return torch.ops.veloxseg.upsample_trilinear(x, list(size)) if USE_DISPATCH else m.upsample_trilinear(x, *size)
+        return torch.ops.veloxseg.upsample_trilinear(x, list(size))
     return _UpsampleFn.apply(x, size)
 
 
@@ -1450,9 +1420,9 @@ class _GramFn(torch.autograd.Function):
 
 
 def gram(x):
-    m = _cpp_node("small") if x.is_cuda else None
+    m = _cpp() if x.is_cuda else None
     if m is not None:
-        return torch.ops.veloxseg.gram(x) if USE_DISPATCH else m.gram(x)
+        return torch.ops.veloxseg.gram(x)
     return _GramFn.apply(x)
 
 

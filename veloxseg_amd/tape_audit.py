@@ -76,7 +76,6 @@ class StepDag:
         self.engine = engine
         self.nodes: List[tuple] = []
         self.preds: List[List[int]] = []
-        from . import engine as _E
         self.stage_of: List[int] = []
         gate = self._add_tape("enc_fwd", G["enc_fwd"], [], 0)
         ends = [self._add_tape(f"dec_fwd[{k}]", t, [gate], 1) for k, t in enumerate(G["dec_fwd"])]
@@ -86,8 +85,8 @@ class StepDag:
         fan = self._add(("barrier", None, -1, -1, "end of the decoder-backward fan"), bwd_ends, 3)
         tails = [self._add_tape("enc_bwd", G["enc_bwd"], [fan], 4)]
         if "dec_wg" in G:
-            # one after the other on the fourth lane, beside the encoder backward; with engine.WG_EARLY each behind ITS decoder's backward only (engine._replay)
-            early = _E.WG_EARLY and engine.replay_mode == "tape" and len(G["dec_bwd"]) <= 3
+            # one after the other on the fourth lane, beside the encoder backward; with up to three decoders each behind ITS decoder's backward only (engine._replay)
+            early = len(G["dec_bwd"]) <= 3
             prev = None
             for k in (engine.wg_order() if early else range(len(G["dec_wg"]))):
                 gates = [bwd_ends[k] if early else fan] + ([prev] if prev is not None else [])

@@ -56,9 +56,9 @@ def _axis_counts(starts_axis: Sequence[int], r: int, m: int, device) -> torch.Te
 
 # two window batches in flight (round 6): each forward of a window batch is a ~250-launch tape that leaves most of the chip idle at the reference's sw_batch_size of 2; the next
 # batch's forward is replayed from a second caller stream on a replica of the tape (engine.TapedPredictor.forward_slot) while the first one runs.  The blending stays in the
-# reference's window order -- the accumulation of batch i + 1 waits for the one of batch i -- so the result is bit for bit the sequential one.  VELOXSEG_SW_PIPELINE=0: sequential.
-SW_PIPELINE = os.environ.get("VELOXSEG_SW_PIPELINE", "1") != "0"
-SW_INFLIGHT = max(2, min(4, int(os.environ.get("VELOXSEG_SW_INFLIGHT", "2"))))      # window batches in flight (A/B)
+# reference's window order -- the accumulation of batch i + 1 waits for the one of batch i -- so the result is bit for bit the sequential one.  SW_PIPELINE = False: sequential (tests).
+SW_PIPELINE = True
+SW_INFLIGHT = 2      # window batches in flight
 
 
 def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi):
