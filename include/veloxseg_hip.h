@@ -92,7 +92,7 @@ int vx_expand_bwd_data_mfma(const float* dy_fine, const float* w, float* wt_ws, 
 int vx_expand_set_lds(int on);
 int vx_expand_set_fwd_wlds(int on);   /* A/B knob of vx_expand_fwd_mfma: 1 (default) = the weights of a (c, s1) group staged in LDS once per block, 0 = loaded from global memory per tap */
 /* forward of the same layer (conv 16 -> 64*Cc, k3 p1, PixelShuffle(4) store) as MFMA tiles over an LDS halo; wt_ws: Cout*16*27 floats.
- * Needs D % 4 == 0, H % 4 == 0, W % 16 == 0: returns 1 (and launches nothing) otherwise -- the caller then uses vx_conv_s1. */
+ * Needs D % 4 == 0, H % 4 == 0, W % 4 == 0: returns 1 (and launches nothing) otherwise -- the caller then uses vx_conv_s1. */
 int vx_expand_fwd_mfma(const float* x, const float* w, const float* bias, float* wt_ws, float* y, int B, int Cc, int D, int H, int W, void* stream);
 /* patch-expand weight (+bias) gradient on fp32 MFMA: x (B,16,D,H,W) coarse input, xcl_ws = B*D*H*W*16 floats (channels-last copy made here),
  * dy_fine (B,Cc,4D,4H,4W); dw (64*Cc,16,3,3,3) +=, db (64*Cc) += */
@@ -111,7 +111,8 @@ int vx_expand_wgrad_mfma_split_h(const float* x, const void* dy_fine, float* dw,
                                  int ns, int dy_h16, void* stream);
 /* bf16 opt-in mode (BASELINE configs[1]: the BraTS bf16 line): the same two layers with bf16 MFMA operands (v_mfma_f32_16x16x32_bf16), fp32
  * accumulation and fp32 tensors in HBM; weights and activations are rounded to bf16 (nearest-even) on their way into the MFMA.  Same arguments and
- * workspaces as the fp32 entries above; return 1 = shape not covered (D, H % 4, W % 16), the caller then uses the fp32 entry. */
+ * workspaces as the fp32 entries above; return 1 = shape not covered (D % 4, H % 4 or W % 4 != 0; nothing is launched and the output is left as it was), the caller
+ * then uses the fp32 entry.  Any W % 4 == 0 is taken: a row's last 16-wide tile may be partly empty (W = 24, 40: the shipped 96^3 geometry). */
 int vx_expand_fwd_mfma_bf16(const float* x, const float* w, const float* bias, float* wt_ws, float* y, int B, int Cc, int D, int H, int W, void* stream);
 int vx_expand_bwd_data_mfma_bf16(const float* dy_fine, const float* w, float* wt_ws, float* dx, int B, int Cc, int D, int H, int W, int accumulate, void* stream);
 /* 1x1x1 convolutions: thread-per-voxel with scalar-path weights (fwd / bwd_data; Cin % 4 == 0), fp32-MFMA GEMM over the voxel

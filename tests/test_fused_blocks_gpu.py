@@ -233,7 +233,9 @@ def test_jlc_block_backward_uses_the_pieces_mode_of_its_forward():
 def test_jlc_toeplitz_mfma_convs_vs_fp64_and_valu_kernels(case, pieces):
     """csrc/jlc_mfma.hip (the three grouped convs of conv_blocks.py:51-58 and their input gradient as Toeplitz GEMMs on the bf16 matrix pipe) against an fp64 torch
     convolution and against the fp32 VALU kernels of csrc/jlc.hip through the C ABI.  pieces = 3 (six piece products = the fp32 product): error within 3x the VALU
-    kernels' own (fp32 summation noise), per-tile statistics summing to the tensor's; pieces = 1 (bf16 opt-in operands): 2^-8-level relative error, fp32 sums."""
+    kernels' own (fp32 summation noise), per-tile statistics summing to the tensor's; pieces = 1 (bf16 opt-in operands): the same bound against the fp64 convolution of
+    the operands as the kernel rounds them (x, w and g_3 / g_5 to bf16, nearest even; the 1x1 term of the input gradient and d_o are added in fp32, unrounded): bf16 x bf16
+    products are exact in fp32, so what is left is fp32 summation noise -- a dropped tap would be ~1e-2."""
     import torch.nn.functional as TF
     from veloxseg_amd import _hip as H
     _, B, C, G, (D, Hh, W) = case
@@ -265,28 +267,26 @@ def test_jlc_toeplitz_mfma_convs_vs_fp64_and_valu_kernels(case, pieces):
         H.call("vx_jlc_tz_bwd", g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), H.P(img), H.P(ws[0]), H.P(d_o), H.P(dx_new), B, C, G, D, Hh, W, st)
         torch.cuda.synchronize()
         exact = pieces in (3, 22)        # 3 bf16 pieces (six products) or two scaled fp16 pieces (22 significant bits, three products): fp32-level error
+        rnd = (lambda t: t.double()) if exact else (lambda t: t.bfloat16().double())      # pieces = 1: the operands as the kernel rounds them
         for i, k in enumerate((1, 3, 5)):
             ref = TF.conv3d(x.double(), ws[i].double(), bs[i].double(), padding=k // 2, groups=G)
+            ref_new = ref if exact else TF.conv3d(rnd(x), rnd(ws[i]), bs[i].double(), padding=k // 2, groups=G)
             sc = float(ref.abs().max())
-            e_old, e_new = float((y_old[i].double() - ref).abs().max()) / sc, float((y_new[i].double() - ref).abs().max()) / sc
-            if exact:
-                assert e_new <= max(3.0 * e_old, 2e-6), (k, e_old, e_new)
-            else:
-                assert e_new <= 2e-2, (k, e_new)
+            e_old, e_new = float((y_old[i].double() - ref).abs().max()) / sc, float((y_new[i].double() - ref_new).abs().max()) / sc
+            assert e_new <= max(3.0 * e_old, 2e-6), (k, e_old, e_new)
             # per-tile (sum, sumsq) partials fold to the statistics of what the kernel STORED
             s_new = p_new[i].sum(1).view(B, C, 2)
             yk = y_new[i].double()
             assert torch.allclose(s_new[..., 0], yk.sum((2, 3, 4)), rtol=1e-5, atol=1e-3 * sc)
             assert torch.allclose(s_new[..., 1], (yk * yk).sum((2, 3, 4)), rtol=1e-5, atol=1e-3 * sc * sc)
-        ref = d_o.double()
+        ref, ref_new = d_o.double(), d_o.double()
         for i, k in enumerate((1, 3, 5)):
             ref = ref + TF.conv_transpose3d(g[i].double(), ws[i].double(), None, padding=k // 2, groups=G)
+            ref_new = ref_new + (TF.conv_transpose3d(g[i].double(), ws[i].double(), None, padding=k // 2, groups=G) if exact or k == 1 else
+                                 TF.conv_transpose3d(rnd(g[i]), rnd(ws[i]), None, padding=k // 2, groups=G))
         sc = float(ref.abs().max())
-        e_old, e_new = float((dx_old.double() - ref).abs().max()) / sc, float((dx_new.double() - ref).abs().max()) / sc
-        if exact:
-            assert e_new <= max(3.0 * e_old, 2e-6), (e_old, e_new)
-        else:
-            assert e_new <= 2e-2, e_new
+        e_old, e_new = float((dx_old.double() - ref).abs().max()) / sc, float((dx_new.double() - ref_new).abs().max()) / sc
+        assert e_new <= max(3.0 * e_old, 2e-6), (e_old, e_new)
     finally:
         H.call("vx_jlc_tz_set_pieces", 22)          # (the library default)
         H.call("vx_jlc_tz_set_min_voxels", 1024)

@@ -420,7 +420,7 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
                     vx_ldt<TPW>(xs + (long)ch * V + vc, xv);
 #pragma unroll
                     for (int t = 0; t < TPW; ++t) {
-                        const float d = du[cb][t][i];
+                        const float d = vx_round_as<TI>(du[cb][t][i]);      // (16-bit dn: the InstanceNorm-backward sums are those of the values vx_jlc_mid_bwd loads)
                         o[t] = d;
                         S1[cb][i] += d;
                         S2[cb][i] = fmaf(d, (xv[t] - mu) * rs, S2[cb][i]);
