@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time vx_mlp_fwd / vx_mlp_bwd (csrc/mlp.hip) alone at the bench shapes; at the bench shapes."""
+"""Time vx_mlp_fwd / vx_mlp_bwd (csrc/mlp.hip) alone at the bench shapes (C = 16, R = 48, V = 32768) and at the smallest volume of the 64-voxel waves."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import veloxseg_amd  # noqa
@@ -33,8 +33,8 @@ def run(C, R, V, norm, p, B=4, reps=20):
         for _ in range(reps): f()
         e1.record(); torch.cuda.synchronize()
         res.append(e0.elapsed_time(e1) / reps * 1e3)
-    print(f"C={C} R={R} V={V} norm={norm} p={p} dbg={os.environ.get('VX_MLP_DBG', '0')}: fwd {res[0]:.1f} us  bwd {res[1]:.1f} us", flush=True)
+    print(f"C={C} R={R} V={V} norm={norm} p={p}: fwd {res[0]:.1f} us  bwd {res[1]:.1f} us", flush=True)
 
-for C, R, V in ((16, 48, 32768), (32, 96, 4096)):
+for C, R, V in ((16, 48, 32768), (16, 48, 16384)):
     for norm, p in ((0, 0.0), (0, 0.1), (1, 0.1)):
         run(C, R, V, norm, p)

@@ -10,10 +10,14 @@
 //   * "N chain": a = W1 . n with the voxels on the COLUMNS.  The accumulator registers of a (rows 4*(l/16)+i) are, register by register, valid
 //     B operands of the next GEMM whose reduction runs over those rows: z = W2 . h and, backward, du = W1^T . da chain without any data movement;
 //     the weights are the A operands, staged once per block in LDS in operand order (one conflict-free ds_read_b32 per MFMA);
-//   * "T pass" (backward): the same products with the voxels on the ROWS (the x / dout registers of the N chain serve as A operands, the same LDS
-//     weight images as B operands).  Its accumulators h^T, da^T have the voxel index on l/16 -- exactly the A operand of the weight-gradient
-//     GEMMs dW2^T = h . dz^T, dW1 = da . n^T whose reduction runs over voxels; dz^T / n^T come straight from global memory (16-byte loads).
-//     So both weight gradients, the bias gradients and the norm statistics of the backward pass are formed in registers, with no LDS transposes.
+//   * backward, per block of 16 hidden rows: a = W1 . n and dh = W2^T . dz on the N chain; h = gelu(a) mask1 and da = dh mask1 gelu'(a) are formed ONCE, in the
+//     accumulator layout.  da chains into du = W1^T . da as it stands.  The weight-gradient GEMMs dW2^T = h . dz^T, dW1 = da . n^T reduce over voxels and want the voxel
+//     index on l/16 in both operands: h / da (A operands) and, once per trip, n / dz (B operands) cross a per-wave LDS tile of 16 rows x 16 TPW voxels (row stride
+//     16 TPW + 4 floats: 16-byte writes in the N layout, 16-byte reads in the operand layout, both conflict-free).  Nothing is recomputed or loaded twice for them,
+//     and the dropout masks are drawn once (N layout);
+//   * backward geometry: one trip of 16 TPW voxels per wave; 8 waves per block (512 threads) for V >= 32768, 4 below; <= 256 registers, no scratch: two waves per SIMD,
+//     so one wave's MFMAs run behind the other's Philox / GELU VALU work.  Per block: weight images staged once, every wave lays its dW tiles and row sums out in its
+//     own LDS region (over its transpose tiles), one barrier, then each thread sums an element over the waves -> one float atomic per element and block.
 // Dropout masks are those of vx_gelu_drop_* (site 1, element index in the (B,R,V) tensor) and vx_axpy_drop_* (site 2, (B,C,V)): one Philox call
 // per 4 consecutive voxels of a channel (TPW = 4: they sit in one lane; TPW = 1: shared inside a lane quad by a DPP transpose).
 #include "vx_common.h"
@@ -73,30 +77,31 @@ template <int C, int R>
 __device__ __forceinline__ void vx_mlp_stage_rows(float* __restrict__ dst, const float* __restrict__ w, int ld_row, int ld_col, int nthr) {
     // dst[(jb*(C/4)+ks)*64 + l] = w[(16jb + l%16) * ld_row + (4ks + l/16) * ld_col]; fully unrolled (R*C % 256 == 0) so that every load is in flight
     // before the first LDS store: a rolled loop paid one L2 round trip per element
-    (void)nthr;
+    // (nthr = 256 or 512 threads: with 512 the trailing steps fall past the image and are skipped)
     float v[R * C / 256];
 #pragma unroll
     for (int k = 0; k < R * C / 256; ++k) {
-        const int e = threadIdx.x + 256 * k;
+        const int e = threadIdx.x + nthr * k;
         const int l = e & 63, s = e >> 6, ks = s % (C / 4), jb = s / (C / 4);
-        v[k] = w[(long)(16 * jb + (l & 15)) * ld_row + (long)(4 * ks + (l >> 4)) * ld_col];
+        v[k] = e < R * C ? w[(long)(16 * jb + (l & 15)) * ld_row + (long)(4 * ks + (l >> 4)) * ld_col] : 0.0f;
     }
 #pragma unroll
-    for (int k = 0; k < R * C / 256; ++k) dst[threadIdx.x + 256 * k] = v[k];
+    for (int k = 0; k < R * C / 256; ++k)
+        if (threadIdx.x + nthr * k < R * C) dst[threadIdx.x + nthr * k] = v[k];
 }
 template <int C, int R>
 __device__ __forceinline__ void vx_mlp_stage_acc(float* __restrict__ dst, const float* __restrict__ w, int ld_c, int ld_j, int nthr) {
     // dst[((cb*(R/16)+rb)*4+i)*64 + l] = w[(16cb + l%16) * ld_c + (16rb + 4(l/16) + i) * ld_j]
-    (void)nthr;
     float v[R * C / 256];
 #pragma unroll
     for (int k = 0; k < R * C / 256; ++k) {
-        const int e = threadIdx.x + 256 * k;
+        const int e = threadIdx.x + nthr * k;
         const int l = e & 63, s = e >> 6, i = s & 3, rb = (s >> 2) % (R / 16), cb = (s >> 2) / (R / 16);
-        v[k] = w[(long)(16 * cb + (l & 15)) * ld_c + (long)(16 * rb + 4 * (l >> 4) + i) * ld_j];
+        v[k] = e < R * C ? w[(long)(16 * cb + (l & 15)) * ld_c + (long)(16 * rb + 4 * (l >> 4) + i) * ld_j] : 0.0f;
     }
 #pragma unroll
-    for (int k = 0; k < R * C / 256; ++k) dst[threadIdx.x + 256 * k] = v[k];
+    for (int k = 0; k < R * C / 256; ++k)
+        if (threadIdx.x + nthr * k < R * C) dst[threadIdx.x + nthr * k] = v[k];
 }
 
 template <int TPW, typename T> __device__ __forceinline__ void vx_ldt(const T* __restrict__ p, float (&o)[TPW]) {
@@ -237,9 +242,25 @@ __global__ void __launch_bounds__(256) vx_mlp_fwd_k(VxMlp p) {
 }
 
 // --------------------------------------------------------------------------------------------------------------------- backward
+// Per-wave LDS region of the backward kernel (floats): two [16 rows][TS] transpose tiles during the trip, the wave's flush image afterwards
+//   TS = 16 * TPW + 4: the row stride (68 / 20 floats) leaves both sides of the transpose conflict-free -- the N-layout lane (m, q) writes its TPW voxels of row
+//   4q + i at column TPW * m, the A-operand lane (m, q) reads the 4 * TPW consecutive voxels of row m at column 4 * TPW * q (16-byte accesses for TPW = 4)
+template <int C, int R, int TPW> struct VxMlpBwdLds {
+    static constexpr int TS = 16 * TPW + 4;
+    static constexpr int TILE = 16 * TS;
+    static constexpr int NS = R + 3 * C;                     // row sums: db1 (R) | db2 (C) | S1, S2 interleaved (2C)
+    static constexpr int FLUSH = 2 * R * C + NS;             // dW2 (C, R) | dW1 (R, C) | row sums
+    static constexpr int WSTR = (2 * TILE > FLUSH ? 2 * TILE : FLUSH);
+    static constexpr int HEAD = 3 * R * C + R + 2 * C;       // A1 | A3 | A4 | b1 | norm constants
+    static_assert(C == 16, "the transpose tiles hold 16 channels");
+    static_assert(WSTR % 4 == 0 && HEAD % 4 == 0 && TS % 4 == 0, "16-byte LDS accesses");
+};
+
+// One trip of 16 * TPW voxels per wave; blockDim.x / 64 waves per block (8 for V >= 32768, else 4); wave w of block x owns voxels (x * nwaves + w) * 16 * TPW ..
 template <int C, int R, int NORM, int TPW, typename TI = float>
-__global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
-    constexpr int KS = C / 4, RB = R / 16, CB = C / 16, VS = TPW, GV = 16 * TPW;
+__global__ void __launch_bounds__(512) vx_mlp_bwd_k(VxMlp p) {
+    using L = VxMlpBwdLds<C, R, TPW>;
+    constexpr int KS = C / 4, RB = R / 16, CB = C / 16, VS = TPW, GV = 16 * TPW, TS = L::TS;
     extern __shared__ __attribute__((aligned(16))) float vx_mlp_lds[];
     float* __restrict__ A1 = vx_mlp_lds;
     float* __restrict__ A3 = A1 + R * C;
@@ -247,15 +268,13 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
     float* __restrict__ b1s = A4 + R * C;
     float* __restrict__ mu_s = b1s + R;       // IN: mean   | LN: gamma
     float* __restrict__ rs_s = mu_s + C;      // IN: rstd   | LN: beta
-    float* __restrict__ red = rs_s + C;       // flush area: [R*C] dW2^T tiles, [R*C] dW1 tiles, [4][R + 3C] row sums
-    const int tid = threadIdx.x, b = blockIdx.y, lane = tid & 63, wave = tid >> 6;
+    float* wreg = rs_s + C;                   // [nwaves][WSTR]
+    const int tid = threadIdx.x, nthr = blockDim.x, b = blockIdx.y, lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
     const int m = lane & 15, q = lane >> 4;
-    {
-    vx_mlp_stage_rows<C, R>(A1, p.w1, C, 1, 256);           // W1[j][c]
-    vx_mlp_stage_rows<C, R>(A3, p.w2, 1, R, 256);           // W2[c][j] read as [j][c]
-    vx_mlp_stage_acc<C, R>(A4, p.w1, 1, C, 256);            // W1[j][c] read as [c][j]
-    }
-    for (int e = tid; e < R; e += 256) b1s[e] = p.b1[e];
+    vx_mlp_stage_rows<C, R>(A1, p.w1, C, 1, nthr);           // W1[j][c]
+    vx_mlp_stage_rows<C, R>(A3, p.w2, 1, R, nthr);           // W2[c][j] read as [j][c]
+    vx_mlp_stage_acc<C, R>(A4, p.w1, 1, C, nthr);            // W1[j][c] read as [c][j]
+    for (int e = tid; e < R; e += nthr) b1s[e] = p.b1[e];
     if (NORM == 0) vx_mlp_in_stats<C>(p, false, b, mu_s, rs_s, false);
     else if (tid < C) { mu_s[tid] = p.gamma[tid]; rs_s[tid] = p.beta[tid]; }
     __syncthreads();
@@ -264,6 +283,9 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
     const TI* __restrict__ xs = (const TI*)p.x + (long)b * C * V;
     const float* __restrict__ gs = p.dout + (long)b * C * V;
     TI* __restrict__ os = (TI*)p.dn + (long)b * C * V;
+    float* wr = wreg + wave * L::WSTR;                       // this wave's region; only this wave touches it until the flush barrier
+    float* tA = wr;                                          // tile 0: n, then h  = gelu(a) mask1
+    float* tB = wr + L::TILE;                                // tile 1: dz, then da = dh mask1 gelu'(a)
 
     vx_f32x4 aW2[RB][CB], aW1[RB][CB];                      // D tiles: reg i = (j = 16jb + 4q + i, c = 16cb + m)
     float sb1[RB], sb2[CB], S1[CB][4], S2[CB][4];           // lane partials: db1 (j = 16jb + m), db2 (c = 16cb + m), norm sums (c = 16cb + 4q + i)
@@ -280,23 +302,12 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
         for (int i = 0; i < 4; ++i) { S1[cb][i] = 0.0f; S2[cb][i] = 0.0f; }
     }
 
-    // The dropout masks are needed twice per element: in the N layout (voxels on the MFMA columns: the input-gradient chain) and in the T layout (voxels on the rows:
-    // the weight-gradient products).  Drawing them twice was 32 Philox calls per lane and trip -- over a third of this kernel's issue slots.  They are drawn once, in the
-    // N layout; every lane leaves its keep bits (bit 16 rb + 4 i + t: row 16 rb + 4 q + i of site 1, bit 16 RB + 4 ks + t: channel 4 ks + q of site 2; voxel vl + t) in
-    // a per-wave LDS record, and the T pass picks the nibbles of its own (row, 4 voxels) out of the records of the four lanes that drew them.  (`red` is idle until
-    // the flush; LDS operations of one wave are executed in order.)
-    constexpr int MB2 = 16 * RB, MDW = (16 * RB + 4 * KS + 31) / 32;
-    uint32_t* __restrict__ mrec = reinterpret_cast<uint32_t*>(red) + wave * 64 * MDW;      // [MDW][64 lanes]
-    for (int it = 0; it < p.iters; ++it) {
-        const long v0 = (((long)blockIdx.x * p.iters + it) * 4 + wave) * GV;
-        if (v0 >= V) break;                                    // wave-uniform
+    const long v0 = ((long)blockIdx.x * nwaves + wave) * GV;
+    if (v0 < V) {                                              // wave-uniform; a wave past the end flushes zeros
         const long vl = v0 + VS * m;
         const bool live = vl < V;
-        const long vc = live ? vl : V - VS;
+        const long vc = live ? vl : V - VS;                    // idle lanes load a valid address, carry dz = 0 and store nothing
         const float lz = live ? 1.0f : 0.0f;
-        uint32_t rec[MDW];
-#pragma unroll
-        for (int k = 0; k < MDW; ++k) rec[k] = 0u;
         // ---- N-layout operands: channel 4ks + q, voxels vl .. vl + TPW - 1
         float n[KS][TPW], dz[KS][TPW], uu[TPW], rr[TPW];
         vx_mlp_load_n<C, NORM, TPW, TI>(xs, V, vc, q, mu_s, rs_s, p.eps, n, uu, rr);
@@ -308,10 +319,7 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
                 float m2[4];
                 vx_masks_vox4(d2, (uint64_t)b * C + 4 * ks + q, V, vc, m2);
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    dz[ks][t] *= m2[t] * lz;
-                    rec[(MB2 + 4 * ks + t) >> 5] |= (m2[t] != 0.0f ? 1u : 0u) << ((MB2 + 4 * ks + t) & 31);
-                }
+                for (int t = 0; t < 4; ++t) dz[ks][t] *= m2[t] * lz;
             }
         } else {
 #pragma unroll
@@ -322,7 +330,28 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
                 for (int s = 0; s < 4; ++s) dz[k0 + s][0] *= m2[s] * lz;
             }
         }
-        // ---- N chain: du = W1^T ( (W2^T dz) * mask1 * gelu'(a) ),  a = W1 n + b1
+        // ---- n and the masked dz once more with the voxels on l / 16: the B operands of the two weight-gradient products (reduction over voxels).
+        //      xT[cb][f][e] = (channel 16cb + m, voxel v0 + 4 TPW q + 4 f + e), through the wave's tiles
+        float nT[CB][TPW][4], dzT[CB][TPW][4];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            vx_stt<TPW>(tA + (4 * ks + q) * TS + VS * m, n[ks]);
+            vx_stt<TPW>(tB + (4 * ks + q) * TS + VS * m, dz[ks]);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int f = 0; f < TPW; ++f) {
+                const float4 n4 = vx_ld4(tA, (long)((16 * cb + m) * TS + 4 * VS * q + 4 * f));
+                const float4 g4 = vx_ld4(tB, (long)((16 * cb + m) * TS + 4 * VS * q + 4 * f));
+                nT[cb][f][0] = n4.x; nT[cb][f][1] = n4.y; nT[cb][f][2] = n4.z; nT[cb][f][3] = n4.w;
+                dzT[cb][f][0] = g4.x; dzT[cb][f][1] = g4.y; dzT[cb][f][2] = g4.z; dzT[cb][f][3] = g4.w;
+                sb2[cb] += (g4.x + g4.y) + (g4.z + g4.w);
+            }
+        __builtin_amdgcn_wave_barrier();
+        // ---- per block of 16 hidden rows: a = W1 n + b1, dh = W2^T dz; h = gelu(a) mask1 and da = dh mask1 gelu'(a) are formed ONCE, in the accumulator layout.
+        //      da feeds du = W1^T da as it stands; h and da go through the tiles to the A-operand layout of dW2^T += h dz^T, dW1 += da n^T
         vx_f32x4 du[CB][TPW];
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
@@ -343,23 +372,25 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
 #pragma unroll
                 for (int t = 0; t < TPW; ++t) { a[t] = VX_MFMA(w1a, n[ks][t], a[t]); dh[t] = VX_MFMA(w2a, dz[ks][t], dh[t]); }
             }
-            if constexpr (TPW == 4) {
+            float m1r[4] = {1.f, 1.f, 1.f, 1.f};
+            if constexpr (TPW == 1) vx_masks_rows4(d1, (uint64_t)b * R + 16 * rb + 4 * q, 1, V, vc, m1r);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float m1[4];
-                    vx_masks_vox4(d1, (uint64_t)b * R + 16 * rb + 4 * q + i, V, vc, m1);
+            for (int i = 0; i < 4; ++i) {
+                float m1[4], hv[TPW], dv[TPW];
+                if constexpr (TPW == 4) vx_masks_vox4(d1, (uint64_t)b * R + 16 * rb + 4 * q + i, V, vc, m1);
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        dh[t][i] *= m1[t] * vx_gelu_grad_fast(a[t][i]);
-                        rec[(16 * rb + 4 * i + t) >> 5] |= (m1[t] != 0.0f ? 1u : 0u) << ((16 * rb + 4 * i + t) & 31);
-                    }
+                for (int t = 0; t < TPW; ++t) {
+                    const float mk = TPW == 4 ? m1[t] : m1r[i], av = a[t][i];
+                    float cdf, pdf;
+                    vx_cdf_pdf(av, cdf, pdf);
+                    dh[t][i] *= mk * fmaf(av, pdf, cdf);
+                    dv[t] = dh[t][i];
+                    hv[t] = av * cdf * mk;
                 }
-            } else {
-                float m1[4];
-                vx_masks_rows4(d1, (uint64_t)b * R + 16 * rb + 4 * q, 1, V, vc, m1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) dh[0][i] *= m1[i] * vx_gelu_grad_fast(a[0][i]);
+                vx_stt<TPW>(tA + (4 * q + i) * TS + VS * m, hv);
+                vx_stt<TPW>(tB + (4 * q + i) * TS + VS * m, dv);
             }
+            __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -368,6 +399,21 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
 #pragma unroll
                     for (int t = 0; t < TPW; ++t) du[cb][t] = VX_MFMA(wa, dh[t][i], du[cb][t]);
                 }
+#pragma unroll
+            for (int f = 0; f < TPW; ++f) {
+                const float4 h4 = vx_ld4(tA, (long)(m * TS + 4 * VS * q + 4 * f));
+                const float4 a4 = vx_ld4(tB, (long)(m * TS + 4 * VS * q + 4 * f));
+                const float hT[4] = {h4.x, h4.y, h4.z, h4.w}, daT[4] = {a4.x, a4.y, a4.z, a4.w};
+                sb1[rb] += (a4.x + a4.y) + (a4.z + a4.w);
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        aW2[rb][cb] = VX_MFMA(hT[e], dzT[cb][f][e], aW2[rb][cb]);
+                        aW1[rb][cb] = VX_MFMA(daT[e], nT[cb][f][e], aW1[rb][cb]);
+                    }
+            }
+            __builtin_amdgcn_wave_barrier();
         }
         // ---- norm backward (+ residual) in the accumulator layout: channel 16cb + 4q + i, voxels vl ..
         if (NORM == 1) {
@@ -428,150 +474,33 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
                     if (live) vx_stt<TPW>(os + (long)ch * V + vl, o);
                 }
         }
-        // ---- T pass: voxels on the rows.  Tile t = voxels {v0 + VS*m' + t}; accumulator reg i <-> m' = 4q + i <-> voxel v0 + VS*(4q+i) + t.
-        //      T-layout global operands: channel 16cb + m, the lane's 4*TPW consecutive voxels v0 + 4*VS*q ..
-        const long vt = v0 + 4 * VS * q;                       // multiple of 4
-        if constexpr (TPW == 4) {
-            if (d1.on || d2.on) {
+    }
+    // ---- flush: every wave lays its tiles and row sums out in its own region (over its transpose tiles), then each thread sums one element over the waves:
+    //      one barrier, one float atomic (or partial-sum store) per element and block
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int k = 0; k < MDW; ++k) mrec[k * 64 + lane] = rec[k];
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        float dzT[CB][TPW][4], nT[CB][TPW][4];
+    for (int jb = 0; jb < RB; ++jb)
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
-            const int ch = 16 * cb + m;
-            const float c0 = mu_s[ch], c1 = rs_s[ch];
+            // dW2 in destination order (C, R): the four registers are four consecutive j
+            vx_st4(wr, (long)((16 * cb + m) * R + 16 * jb + 4 * q), make_float4(aW2[jb][cb][0], aW2[jb][cb][1], aW2[jb][cb][2], aW2[jb][cb][3]));
 #pragma unroll
-            for (int f = 0; f < TPW; ++f) {                    // f-th float4 of the lane's run: TPW = 4 -> (i = f, t = component); TPW = 1 -> (t = 0, i = component)
-                const long vf = vt + 4 * f;
-                const bool lf = vf < V;
-                const long va = lf ? vf : V - 4;
-                const float4 g4 = *reinterpret_cast<const float4*>(gs + (long)ch * V + va);
-                const float4 x4 = vx_ld4(xs, (long)ch * V + va);
-                float m2[4];
-                if constexpr (TPW == 4) {
-                    // voxels v0 + 4 (4 q + f) + e of channel 16 cb + m = 4 ks + q': drawn by lane (m' = 4 q + f, q' = m & 3), ks = 4 cb + (m >> 2)
-                    if (d2.on) {
-                        const uint32_t nib = mrec[((MB2 + 16 * cb) >> 5) * 64 + 16 * (m & 3) + 4 * q + f] >> (((MB2 + 16 * cb) & 31) + 4 * (m >> 2));
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) m2[e] = ((nib >> e) & 1u) ? d2.inv_keep : 0.0f;
-                    } else { m2[0] = m2[1] = m2[2] = m2[3] = 1.0f; }
-                } else vx_masks_vox4(d2, (uint64_t)b * C + ch, V, va, m2);
-                const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int t = TPW == 4 ? e : 0, i = TPW == 4 ? f : e;
-                    const float dzv = lf ? gv[e] * m2[e] : 0.0f;
-                    dzT[cb][t][i] = dzv;
-                    sb2[cb] += dzv;
-                    float nv;
-                    if (NORM == 1) {
-                        // the per-voxel statistics live in the N layout at the lanes with l%16 == 4q + i: fetch them from lane 4q + i
-                        const float u = __shfl(uu[t], 4 * q + i, 64), r = __shfl(rr[t], 4 * q + i, 64);
-                        nv = fmaf(c0, (xv[e] - u) * r, c1);
-                    } else nv = (xv[e] - c0) * c1;
-                    nT[cb][t][i] = nv;
-                }
-            }
+            for (int i = 0; i < 4; ++i) wr[R * C + (16 * jb + 4 * q + i) * C + 16 * cb + m] = aW1[jb][cb][i];      // dW1 (R, C)
         }
-#pragma unroll
-        for (int jb = 0; jb < RB; ++jb) {
-            vx_f32x4 aT[TPW], hT[TPW];
-            const float bj = b1s[16 * jb + m];
-#pragma unroll
-            for (int t = 0; t < TPW; ++t) { aT[t] = (vx_f32x4){bj, bj, bj, bj}; hT[t] = (vx_f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const float w1b = A1[(jb * KS + ks) * 64 + lane], w2b = A3[(jb * KS + ks) * 64 + lane];
-#pragma unroll
-                for (int t = 0; t < TPW; ++t) { aT[t] = VX_MFMA(n[ks][t], w1b, aT[t]); hT[t] = VX_MFMA(dz[ks][t], w2b, hT[t]); }     // hT holds dh^T for now
-            }
-            // element (j = 16jb + m, voxel v0 + VS*(4q+i) + t): h^T = gelu(a) m1 -> aT ; da^T = dh m1 gelu'(a) -> hT
-#pragma unroll
-            for (int f = 0; f < TPW; ++f) {
-                const long vf = vt + 4 * f;
-                const long va = vf < V ? vf : V - 4;
-                float m1[4];
-                if constexpr (TPW == 4) {
-                    // row 16 jb + m = 16 rb + 4 q' + i: drawn by lane (m' = 4 q + f, q' = m >> 2) with i = m & 3
-                    if (d1.on) {
-                        const uint32_t nib = mrec[((16 * jb) >> 5) * 64 + 16 * (m >> 2) + 4 * q + f] >> (((16 * jb) & 31) + 4 * (m & 3));
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) m1[e] = ((nib >> e) & 1u) ? d1.inv_keep : 0.0f;
-                    } else { m1[0] = m1[1] = m1[2] = m1[3] = 1.0f; }
-                    (void)va;
-                } else vx_masks_vox4(d1, (uint64_t)b * R + 16 * jb + m, V, va, m1);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int t = TPW == 4 ? e : 0, i = TPW == 4 ? f : e;
-                    const float av = aT[t][i];
-                    float cdf, pdf;
-                    vx_cdf_pdf(av, cdf, pdf);
-                    const float da = hT[t][i] * m1[e] * (cdf + av * pdf);
-                    aT[t][i] = av * cdf * m1[e];
-                    hT[t][i] = da;
-                    sb1[jb] += da;
-                }
-            }
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                for (int t = 0; t < TPW; ++t)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        aW2[jb][cb] = VX_MFMA(aT[t][i], dzT[cb][t][i], aW2[jb][cb]);
-                        aW1[jb][cb] = VX_MFMA(hT[t][i], nT[cb][t][i], aW1[jb][cb]);
-                    }
-        }
-    }
-    // ---- flush: the 4 waves add their tiles into one LDS image in turn, then one float atomic per element and block
-    __syncthreads();
-    for (int wv = 0; wv < 4; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int jb = 0; jb < RB; ++jb)
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int j = 16 * jb + 4 * q + i, c = 16 * cb + m;
-                        float* d2p = red + j * C + c;
-                        float* d1p = red + R * C + j * C + c;
-                        *d2p = (wv == 0) ? aW2[jb][cb][i] : *d2p + aW2[jb][cb][i];
-                        *d1p = (wv == 0) ? aW1[jb][cb][i] : *d1p + aW1[jb][cb][i];
-                    }
-        }
-        __syncthreads();
-    }
-    // one float atomic per element and block, 256 contiguous bytes per wave instruction; the blocks start at different offsets so that the
-    // blocks that finish together do not walk the same addresses in lock step (adds to one address serialise at ~25 ns each)
-    {
-        const int rot = (int)((blockIdx.x + gridDim.x * blockIdx.y) * 1031u % (unsigned)(R * C / 64)) * 64;
-        for (int k = tid; k < R * C; k += 256) {
-            int e = k + rot;
-            e = e >= R * C ? e - R * C : e;
-            const int c = e / R, j = e - c * R;
-            atomicAdd(p.dw2 + e, red[j * C + c]);              // dW2 (C, R), destination order
-            atomicAdd(p.dw1 + e, red[R * C + e]);              // dW1 (R, C)
-        }
-    }
-    // row sums: bias gradients (reduce over q: lanes m, m+16, m+32, m+48) and norm sums (reduce over m: the 16 lanes of a q group), then over the
-    // 4 waves through LDS -> ONE atomic (or partial-sum store) per element and block
-    float* __restrict__ rsum = red + 2 * R * C;               // [wave][R + 3C]: db1 (R) | db2 (C) | S1,S2 interleaved (2C)
-    constexpr int NS = R + 3 * C;
+    // row sums: bias gradients (reduce over q: lanes m, m+16, m+32, m+48) and norm sums (reduce over m: the 16 lanes of a q group)
+    float* rsum = wr + 2 * R * C;
+    constexpr int NS = L::NS;
 #pragma unroll
     for (int jb = 0; jb < RB; ++jb) {
         float s = sb1[jb];
         s += __shfl_xor(s, 16, 64); s += __shfl_xor(s, 32, 64);
-        if (q == 0) rsum[wave * NS + 16 * jb + m] = s;
+        if (q == 0) rsum[16 * jb + m] = s;
     }
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
         float s = sb2[cb];
         s += __shfl_xor(s, 16, 64); s += __shfl_xor(s, 32, 64);
-        if (q == 0) rsum[wave * NS + R + 16 * cb + m] = s;
+        if (q == 0) rsum[R + 16 * cb + m] = s;
     }
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
@@ -580,11 +509,28 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
             float t1 = S1[cb][i], t2 = S2[cb][i];
 #pragma unroll
             for (int o = 1; o < 16; o <<= 1) { t1 += __shfl_xor(t1, o, 64); t2 += __shfl_xor(t2, o, 64); }
-            if (m == 0) { rsum[wave * NS + R + C + 2 * (16 * cb + 4 * q + i)] = t1; rsum[wave * NS + R + C + 2 * (16 * cb + 4 * q + i) + 1] = t2; }
+            if (m == 0) { rsum[R + C + 2 * (16 * cb + 4 * q + i)] = t1; rsum[R + C + 2 * (16 * cb + 4 * q + i) + 1] = t2; }
         }
     __syncthreads();
+    // element k of the block's [dW2 | dW1] image, summed over the waves in groups of four (a fixed order: nothing below depends on timing but the atomics).
+    // 256 contiguous bytes per wave instruction; the blocks start at different offsets so that the blocks that finish together do not walk the same
+    // addresses in lock step (adds to one address serialise at ~25 ns each)
+    const int rot = (int)((blockIdx.x + gridDim.x * blockIdx.y) * 1031u % (unsigned)(R * C / 64)) * 64;
+    for (int k = tid; k < 2 * R * C; k += nthr) {
+        const int half = k >= R * C ? 1 : 0;                   // wave-uniform (R * C % 64 == 0)
+        int e = k - half * R * C + rot;
+        e = e >= R * C ? e - R * C : e;
+        const float* src = wreg + half * R * C + e;
+        float s = 0.0f;
+        for (int w = 0; w < nwaves; w += 4)
+            s += (src[w * L::WSTR] + src[(w + 1) * L::WSTR]) + (src[(w + 2) * L::WSTR] + src[(w + 3) * L::WSTR]);
+        atomicAdd((half ? p.dw1 : p.dw2) + e, s);
+    }
     if (tid < NS) {
-        const float s = (rsum[tid] + rsum[NS + tid]) + (rsum[2 * NS + tid] + rsum[3 * NS + tid]);
+        const float* src = wreg + 2 * R * C + tid;
+        float s = (src[0] + src[L::WSTR]) + (src[2 * L::WSTR] + src[3 * L::WSTR]);
+        for (int w = 4; w < nwaves; w += 4)
+            s += (src[w * L::WSTR] + src[(w + 1) * L::WSTR]) + (src[(w + 2) * L::WSTR] + src[(w + 3) * L::WSTR]);
         if (tid < R) atomicAdd(p.db1 + tid, s);
         else if (tid < R + C) atomicAdd(p.db2 + (tid - R), s);
         else {
@@ -596,11 +542,12 @@ __global__ void __launch_bounds__(256) vx_mlp_bwd_k(VxMlp p) {
 }
 
 // --------------------------------------------------------------------------------------------------------------------- host
-static size_t vx_mlp_bwd_lds(int C, int R) { return ((size_t)5 * R * C + R + 2 * C + 4 * (R + 3 * C)) * sizeof(float); }
 // batch-size independent launch geometry (a sample's partial sums are folded in the same order whatever it is batched with)
 static int vx_mlp_tpw(long V) { return V >= 16384 ? 4 : 1; }
 static int vx_mlp_iters(long V) { return V >= 32768 ? 2 : 1; }
 static int vx_mlp_blocks(long V) { return vx_cdiv(V, (long)64 * vx_mlp_tpw(V) * vx_mlp_iters(V)); }
+// backward: one trip of 16 * tpw voxels per wave, 4 * iters waves per block (8 waves = 512 threads for V >= 32768), so the grid is vx_mlp_blocks(V) for every V
+static int vx_mlp_bwd_threads(long V) { return 256 * vx_mlp_iters(V); }
 
 extern "C" int vx_mlp_supported(int C, int R, long V) {
     // C = 16 only.  The C = 32 instances (R = 96 / 64) were compiled until round 5 and never launched by default (C >= 32 runs on the tile-GEMM chains of pwa_fused.hip,
@@ -652,10 +599,12 @@ extern "C" int vx_mlp_fwd(const float* x, int norm, const double* part, int npar
 }
 
 template <int C, int R, int NORM, int TPW, typename TI = float>
-static void vx_mlp_bwd_launch(const VxMlp& p, dim3 grid, size_t shm, hipStream_t st) {
+static void vx_mlp_bwd_launch(const VxMlp& p, dim3 grid, hipStream_t st) {
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute((const void*)vx_mlp_bwd_k<C, R, NORM, TPW, TI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    vx_mlp_bwd_k<C, R, NORM, TPW, TI><<<grid, dim3(256), shm, st>>>(p);
+    const int nthr = vx_mlp_bwd_threads(p.V);
+    const size_t shm = (size_t)(VxMlpBwdLds<C, R, TPW>::HEAD + (nthr / 64) * VxMlpBwdLds<C, R, TPW>::WSTR) * sizeof(float);
+    vx_mlp_bwd_k<C, R, NORM, TPW, TI><<<grid, dim3(nthr), shm, st>>>(p);
 }
 
 // h16 != 0 (norm = 0 only): x (= o of the JLC block) and the returned dx (= dn) are vx_bf16 arrays; dout stays fp32
@@ -671,20 +620,18 @@ extern "C" int vx_mlp_bwd_h(const void* x, int norm, const float* stats, const f
     p.x = x; p.gamma = gamma; p.beta = beta; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.dout = dout;
     p.stats = const_cast<float*>(stats); p.dn = dx; p.part_out = part_out; p.dgamma = dgamma; p.dbeta = dbeta;
     p.dw1 = dw1; p.db1 = db1; p.dw2 = dw2; p.db2 = db2; p.V = V; p.eps = eps;
-    p.iters = vx_mlp_iters(V);
     p.d1 = vx_mk_drop(seed_ptr, site1, p1);
     p.d2 = vx_mk_drop(seed_ptr, site2, p2);
     dim3 grid(vx_mlp_blocks(V), B);
-    const size_t shm = vx_mlp_bwd_lds(C, R);
     hipStream_t st = (hipStream_t)stream;
     const int tpw = vx_mlp_tpw(V);
     bool done = false;
 #define VX_MLP_BWD(CC, RR)                                                                                     \
     if (!done && C == CC && R == RR) {                                                                         \
         done = true;                                                                                           \
-        if (norm) { if (tpw == 4) vx_mlp_bwd_launch<CC, RR, 1, 4>(p, grid, shm, st); else vx_mlp_bwd_launch<CC, RR, 1, 1>(p, grid, shm, st); } \
-        else if (h16) { if (tpw == 4) vx_mlp_bwd_launch<CC, RR, 0, 4, vx_bf16>(p, grid, shm, st); else vx_mlp_bwd_launch<CC, RR, 0, 1, vx_bf16>(p, grid, shm, st); } \
-        else { if (tpw == 4) vx_mlp_bwd_launch<CC, RR, 0, 4>(p, grid, shm, st); else vx_mlp_bwd_launch<CC, RR, 0, 1>(p, grid, shm, st); }      \
+        if (norm) { if (tpw == 4) vx_mlp_bwd_launch<CC, RR, 1, 4>(p, grid, st); else vx_mlp_bwd_launch<CC, RR, 1, 1>(p, grid, st); } \
+        else if (h16) { if (tpw == 4) vx_mlp_bwd_launch<CC, RR, 0, 4, vx_bf16>(p, grid, st); else vx_mlp_bwd_launch<CC, RR, 0, 1, vx_bf16>(p, grid, st); } \
+        else { if (tpw == 4) vx_mlp_bwd_launch<CC, RR, 0, 4>(p, grid, st); else vx_mlp_bwd_launch<CC, RR, 0, 1>(p, grid, st); }      \
     }
     VX_MLP_SHAPES(VX_MLP_BWD)
 #undef VX_MLP_BWD
