@@ -422,13 +422,13 @@ def test_instnorm_sum(n, act, res, shape):
         outs = {}
         try:
             for flag in (True, False):
-                F_.USE_IN_ROW = flag
+                F_.set_host_flags(USE_IN_ROW=flag)
                 t = [y.clone().to(d).requires_grad_(True) for y in ys + r]
                 o = g(*t)
                 o.backward(rnd(*shape, seed=77).to(d))
                 outs[flag] = [o.detach()] + [x.grad for x in t]
         finally:
-            F_.USE_IN_ROW = True
+            F_.set_host_flags(USE_IN_ROW=True)
         for a, b in zip(outs[True], outs[False]):
             close(a, b, 1e-5 * max(1.0, float(b.abs().max())), 1e-5, "row vs split")
 
@@ -652,8 +652,7 @@ def test_kernel_variants_agree():
     d = dev()
 
     def run(cfg):
-        for k, v in cfg.items():
-            setattr(F_, k, v)
+        F_.set_host_flags(**cfg)
         torch.manual_seed(0)
         res = []
         for (Cin, Cout, K, G, ps, sp) in [(16, 128, 3, 1, 4, (6, 5, 8)), (16, 16, 5, 4, 1, (8, 8, 8)), (32, 32, 3, 4, 1, (4, 6, 8)), (64, 32, 1, 1, 1, (4, 4, 4)),
@@ -669,10 +668,10 @@ def test_kernel_variants_agree():
         torch.cuda.synchronize()
         return res
 
-    base = dict(WGRAD_ENTRY="vx_conv3d_bwd_weight_tiled", USE_S1=True, USE_EXPAND_MFMA=True, PW_MFMA_MAX_V=4096, USE_GCONV1=True, USE_WGRAD_WS=True)
-    saved = {k: getattr(F_, k) for k in base}            # (restored below: a flag left changed sends every later test of the session down the python operator bodies)
-    ref = run(dict(WGRAD_ENTRY="vx_conv3d_bwd_weight", USE_S1=False, USE_EXPAND_MFMA=False, PW_MFMA_MAX_V=0, USE_GCONV1=False, USE_WGRAD_WS=False))
+    base = dict(WGRAD_UNTILED=False, USE_S1=True, USE_EXPAND_MFMA=True, PW_MFMA_MAX_V=4096, USE_GCONV1=True, USE_WGRAD_WS=True)
+    saved = {k: getattr(F_, k) for k in base}            # (restored below: a flag left changed would select other kernels in every later test of the session)
     try:
+        ref = run(dict(WGRAD_UNTILED=True, USE_S1=False, USE_EXPAND_MFMA=False, PW_MFMA_MAX_V=0, USE_GCONV1=False, USE_WGRAD_WS=False))
         for variant in (base, dict(base, USE_EXPAND_MFMA=False), dict(base, PW_MFMA_MAX_V=0), dict(base, USE_GCONV1=False), dict(base, USE_WGRAD_WS=False)):
             got = run(variant)
             for i, (a, b_) in enumerate(zip(got, ref)):
@@ -688,8 +687,72 @@ def test_kernel_variants_agree():
                 for i, (a, b_) in enumerate(zip(got, ref)):
                     close(a, b_, 2e-5 * max(1.0, float(b_.abs().max())), 1e-4, f"{knob}={val} tensor {i}")
     finally:
-        for k, v in saved.items():
-            setattr(F_, k, v)
+        F_.set_host_flags(**saved)
+
+
+def test_host_flags_reach_the_cpp_dispatch():
+    """Every flag of functional.set_host_flags changes which C-ABI entries the C++ operator bodies call (the names _vxops.profile_begin / profile_end
+    record, read from csrc/_vxops.cpp): a flag that was not forwarded would let the variant tests compare a kernel with itself."""
+    VF = _vf()
+    d = dev()
+    m = VF.cpp_module()
+
+    def conv_names(flags, Cin, Cout, K, G, sp, B=2, ps=1, stride=1, padding=None, x_grad=True):
+        """(forward entries, backward entries) of one conv3d forward + backward under `flags`"""
+        old = VF.set_host_flags(**flags)
+        try:
+            x = rnd(B, Cin, *sp, seed=1).to(d).requires_grad_(x_grad)
+            w = (rnd(Cout, Cin // G, K, K, K, seed=2) * 0.1).to(d).requires_grad_(True)
+            b = rnd(Cout, seed=3).to(d).requires_grad_(True)
+            m.profile_begin()
+            y = VF.conv3d(x, w, b, stride=stride, padding=K // 2 if padding is None else padding, groups=G, pixel_shuffle=ps)
+            fwd = {r[0] for r in m.profile_end()}
+            m.profile_begin()
+            y.backward(torch.ones_like(y))
+            bwd = {r[0] for r in m.profile_end()}
+        finally:
+            VF.set_host_flags(**old)
+        return fwd, bwd
+
+    def both(flag, off, on, **case):
+        return conv_names({flag: off}, **case), conv_names({flag: on}, **case)
+
+    (f0, b0), (f1, b1) = both("USE_S1", False, True, Cin=16, Cout=16, K=5, G=4, sp=(8, 8, 8))
+    assert "vx_conv3d_fwd" in f0 and "vx_conv_s1" not in f0 | b0, (f0, b0)
+    assert "vx_conv_s1" in f1 and "vx_conv3d_fwd" not in f1, f1
+    (f0, b0), (f1, b1) = both("USE_EXPAND_MFMA", False, True, Cin=16, Cout=64, K=3, G=1, sp=(4, 8, 8), ps=4)
+    assert "vx_conv_s1" in f0 and not any(n.startswith("vx_expand_") for n in f0 | b0), (f0, b0)
+    assert any(n.startswith("vx_expand_") for n in b1), (f1, b1)
+    (f0, b0), (f1, b1) = both("PW_MFMA_MAX_V", 0, 4096, Cin=64, Cout=32, K=1, G=1, sp=(4, 4, 4))
+    assert "vx_pw_conv_fwd" in f0 and "vx_pw_conv_mfma" not in f0, f0
+    assert "vx_pw_conv_mfma" in f1 and "vx_pw_conv_fwd" not in f1, f1
+    (f0, b0), (f1, b1) = both("USE_GCONV1", False, True, Cin=16, Cout=16, K=1, G=4, sp=(8, 8, 8))
+    assert "vx_gconv1_bwd_weight" not in b0 and "vx_gconv1_bwd_weight" in b1, (b0, b1)
+    wg = dict(Cin=32, Cout=32, K=3, G=4, sp=(4, 6, 8))
+    (f0, b0), (f1, b1) = both("USE_WGRAD_WS", False, True, **wg)
+    assert "vx_conv3d_bwd_weight_tiled_ws" in b1 and "vx_conv3d_bwd_weight_tiled_ws" not in b0 and "vx_conv3d_bwd_weight_tiled" in b0, (b0, b1)
+    (f0, b0), (f1, b1) = both("WGRAD_UNTILED", False, True, **wg)
+    assert "vx_conv3d_bwd_weight" in b1 and not any(n.startswith("vx_conv3d_bwd_weight_tiled") for n in b1), b1
+    assert "vx_conv3d_bwd_weight" not in b0 and "vx_conv3d_bwd_weight_tiled" in b0, b0
+    (f0, b0), (f1, b1) = both("USE_PATCHIFY", False, True, Cin=1, Cout=16, K=4, G=1, sp=(16, 16, 8), stride=4, padding=0, x_grad=False)
+    assert not any(n.startswith("vx_patchify") or n.startswith("vx_patch_embed") for n in f0 | b0), (f0, b0)
+    assert any(n.startswith("vx_patchify") or n.startswith("vx_patch_embed") for n in f1), f1
+
+    def in_names(flag):
+        old = VF.set_host_flags(USE_IN_ROW=flag)
+        try:
+            y = rnd(2, 4, 8, 8, 8, seed=4).to(d).requires_grad_(True)          # V = 512 <= IN_ROW_MAX
+            m.profile_begin()
+            o = VF.instnorm_sum([y], act=True)
+            o.backward(torch.ones_like(o))
+            return {r[0] for r in m.profile_end()}
+        finally:
+            VF.set_host_flags(**old)
+
+    row, split = in_names(True), in_names(False)
+    assert "vx_in_row_fwd" in row and any(n.startswith("vx_in_row_bwd") for n in row), row
+    assert not any(n.startswith("vx_in_row_") for n in split), split
+    assert any(n in split for n in ("vx_in_fwd_split", "vx_in_stats")) and any(n in split for n in ("vx_in_bwd_split", "vx_in_bwd_db")), split
 
 
 @pytest.mark.parametrize("Cin,Cout,K,sp", [(1, 16, 4, (16, 16, 8)), (2, 8, 2, (8, 12, 16)), (1, 16, 4, (32, 32, 32))])
@@ -705,7 +768,7 @@ def test_patch_conv_via_patchify_matches_direct_conv_and_oracle(Cin, Cout, K, sp
     res = {}
     try:
         for flag in (True, False):
-            F_.USE_PATCHIFY = flag
+            F_.set_host_flags(USE_PATCHIFY=flag)
             w = w0.clone().to(d).requires_grad_(True)
             b = b0.clone().to(d).requires_grad_(True)
             y = VF.conv3d(x.to(d), w, b, stride=K, padding=0)
@@ -714,7 +777,7 @@ def test_patch_conv_via_patchify_matches_direct_conv_and_oracle(Cin, Cout, K, sp
             torch.cuda.synchronize()
             res[flag] = (y.detach().cpu(), w.grad.cpu(), b.grad.cpu())
     finally:
-        F_.USE_PATCHIFY = True
+        F_.set_host_flags(USE_PATCHIFY=True)
     wc, bc = w0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
     yc = F.conv3d(x, wc, bc, stride=K)
     yc.backward(gy)

@@ -127,13 +127,14 @@ def test_fastcall_extension_wraps_every_entry_point():
 
 
 def test_cpp_operator_module_builds_and_loads():
-    """veloxseg_amd._vxops (C++ operator bodies) imports on a CPU-only box and refuses CPU tensors like the python bodies do"""
+    """veloxseg_amd._vxops (C++ operator bodies) imports on a CPU-only box, exposes the node entry points the product path uses and refuses CPU tensors"""
     import pytest
     import torch
     from veloxseg_amd import functional as VF
     m = VF.cpp_module()
     assert m is not None, "run `python -c 'import __graft_entry__ as g; g.build()'`"
-    for name in ("conv_fwd", "conv_bwd", "in_fwd", "in_bwd", "ln_fwd", "ln_bwd", "gelu_fwd", "gelu_bwd", "axpy_fwd", "axpy_bwd", "jlc_fwd", "jlc_bwd", "ffn_fwd", "ffn_bwd"):
+    for name in ("conv", "conv_h", "instnorm", "layernorm", "gelu", "axpy", "jlc", "ffn", "upconv_k2s2", "space_to_depth2", "upsample_trilinear", "gram", "pwa_core", "pw_res", "qkv",
+                 "set_flags"):
         assert hasattr(m, name), name
     with pytest.raises(RuntimeError, match="no CPU"):
         VF.conv3d(torch.zeros(1, 4, 4, 4, 4), torch.zeros(4, 4, 1, 1, 1))

@@ -13,9 +13,7 @@ cfg = dict(cfg, attn_drop=0.0, proj_drop=0.0, conv_drop=0.0)
 x, lab = make_inputs(cfg, B)
 crit = Loss(types.SimpleNamespace(model_name="VeloxSeg"), LOSS_CFG, None, num_modal=2)
 if os.environ.get("NOWS") == "1":
-    VF.USE_WGRAD_WS = False
-    VF.cpp_module().set_flags(VF.USE_S1, VF.USE_EXPAND_MFMA, VF.USE_GCONV1, False, VF.USE_PATCHIFY, VF.USE_IN_ROW, VF.PW_MFMA_MAX_V, VF.IN_ROW_MAX, VF.IN_EPS, VF.LN_EPS)
-    VF._CPP_DEFAULTS = None
+    VF.set_host_flags(USE_WGRAD_WS=False)
 if os.environ.get("WARM") == "1":     # touch the allocator with a big block first
     t_ = torch.empty(64 << 20, device="cuda"); del t_
 torch.manual_seed(3)

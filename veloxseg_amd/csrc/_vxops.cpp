@@ -1,11 +1,10 @@
 // veloxseg_amd._vxops -- the host-side operator bodies in C++ (pybind11 + ATen for allocation only).
 //
 // Why: one eager training step makes ~300 operator calls and ~1050 kernel launches; with the operator bodies in Python the host needs
-// 14-16 ms per step, more than the GPU.  This module runs the SAME sequences of C-ABI calls (include/veloxseg_hip.h) that
-// veloxseg_amd/functional.py runs -- routing, workspace allocation, launches -- without the interpreter in between.  Autograd stays in
-// Python: every entry here is a plain forward or backward function returning tensors plus an opaque state object; functional.py keeps one
-// torch.autograd.Function per operator / composite block and calls these from its forward / backward.  The arithmetic lives in
-// libveloxseg_hip.so either way; this file contains no kernels and no CPU implementation.
+// 14-16 ms per step, more than the GPU.  This module runs the sequences of C-ABI calls (include/veloxseg_hip.h)
+// the operators need -- routing, workspace allocation, launches -- without the interpreter in between.  This is the ONLY host path of these
+// operators: each is a torch::autograd::Function here (forward and backward), reached from veloxseg_amd/functional.py directly or through
+// torch.ops.veloxseg.*.  The arithmetic lives in libveloxseg_hip.so; this file contains no kernels and no CPU implementation.
 //
 // Reference call sites mirrored by the composites: JLC block conv_blocks.py:41-75; FFN tail PWA.py:437 + attention_utils.py:45-71.
 #include <torch/extension.h>
@@ -34,7 +33,7 @@ typedef c10::optional<Tensor> OptT;
 namespace {
 
 struct Flags {
-    bool fuse_blocks = true, use_s1 = true, use_conv_mfma = true, bf16_expand = false, use_expand_mfma = true, use_gconv1 = true, use_wgrad_ws = false, use_patchify = true, use_in_row = true, skip_in_bias = true, in_split2 = true, fuse_res = true, fuse_bwd_add = true;
+    bool fuse_blocks = true, use_s1 = true, use_conv_mfma = true, bf16_expand = false, use_expand_mfma = true, use_gconv1 = true, use_wgrad_ws = false, use_patchify = true, use_in_row = true, wgrad_untiled = false, skip_in_bias = true, in_split2 = true, fuse_res = true, fuse_bwd_add = true;
     int64_t pw_mfma_max_v = 4096, in_row_max = 4096;
     int tile_min_c = 32;              // JLC channel stage on the tile-GEMM kernels (pwa_fused.hip vx_inmlp_*) from this many channels up, mlp.hip below (functional.TILE_MIN_C)
     bool upconv_wgrad_mfma = true;    // (A/B) ConvTranspose weight gradient as one MFMA GEMM (pointwise.hip vx_upconv_k2s2_wgrad) vs the generic strided-conv kernel
@@ -140,6 +139,12 @@ inline void wgrad_submit(void* cur, int dev, std::function<void(void*)> launch) 
 }
 
 // ------------------------------------------------------------------------------------------------------------------- convolution
+// the generic weight gradient: the tiled kernel, or (set_flags(wgrad_untiled = true), A/B tests) the untiled reference kernel
+inline void conv_wgrad_generic(const float* x, const float* x2, int C1, const float* dy, float* dw, float* db, int B, int Cin, int D, int H, int W, int Cout, int K, int S, int P,
+                               int G, int ps, void* s) {
+    if (F.wgrad_untiled) VX(vx_conv3d_bwd_weight, x, x2, C1, dy, dw, db, B, Cin, D, H, W, Cout, K, S, P, G, ps, s);
+    else VX(vx_conv3d_bwd_weight_tiled, x, x2, C1, dy, dw, db, B, Cin, D, H, W, Cout, K, S, P, G, ps, s);
+}
 // bf16 storage mode: the caller of the NEXT patch-expand forward on this thread asks for a 16-bit output (m.conv_h); consumed by conv_fwd_impl
 thread_local bool CONV_OUT_H16 = false;
 struct ConvState {
@@ -350,15 +355,15 @@ void conv_bwd_impl(ConvState& st, const Tensor& dy_in, bool need_x, Tensor& dx, 
                 auto ws = std::make_shared<Tensor>(at::empty({(long)nws}, x.options()));
                 WG.done.push_back([ws](void*) {});
                 VX(vx_down_wgrad_mfma_mx, fp(x), fp(dy), dw, db, mp(*ws), nws, xmax.defined() ? reinterpret_cast<const unsigned*>(xmax.data_ptr()) : nullptr, B, Cin, D, H, W, Cout, s);
-            } else if (G == 1 && ps == 1 && S > 1 && !x2.defined() && vx_conv_wgrad_gather_ok(B, Cin, D, H, W, Cout, K, S, P) == 1) {
+            } else if (G == 1 && ps == 1 && S > 1 && !x2.defined() && !F.wgrad_untiled && vx_conv_wgrad_gather_ok(B, Cin, D, H, W, Cout, K, S, P) == 1) {
                 VX(vx_conv_wgrad_gather_mfma, fp(x), fp(dy), dw, db, B, Cin, D, H, W, Cout, K, S, P, s);      // DownConv levels 2 - 4: gather-GEMM on the fp32 matrix pipe
-            } else if (F.use_wgrad_ws) {
+            } else if (F.use_wgrad_ws && !F.wgrad_untiled) {
                 const int nws = vx_conv3d_bwd_weight_ws_floats(B, Cin, D, H, W, Cout, K, S, P, G, ps);
                 TORCH_CHECK(nws >= 0, "vx_conv3d_bwd_weight_ws_floats failed");
                 auto ws = std::make_shared<Tensor>(nws > 0 ? at::empty({(long)nws}, x.options()) : Tensor());
                 WG.done.push_back([ws](void*) {});
                 VX(vx_conv3d_bwd_weight_tiled_ws, fp(x), fp(x2), C1, fp(dy), dw, db, mp(*ws), nws, B, Cin, D, H, W, Cout, K, S, P, G, ps, s);
-            } else VX(vx_conv3d_bwd_weight_tiled, fp(x), fp(x2), C1, fp(dy), dw, db, B, Cin, D, H, W, Cout, K, S, P, G, ps, s);
+            } else conv_wgrad_generic(fp(x), fp(x2), C1, fp(dy), dw, db, B, Cin, D, H, W, Cout, K, S, P, G, ps, s);
         });
     }
     if (!WG.enabled) WG.done.clear();                        // immediate launches: nothing to keep
@@ -618,7 +623,10 @@ template <class S> c10::intrusive_ptr<Holder<S>> put_state(AutogradContext* ctx)
 template <class S> S& get_state(AutogradContext* ctx) {
     return c10::static_intrusive_pointer_cast<Holder<S>>(ctx->saved_data["st"].toCapsule())->s;
 }
-inline void* cur_stream(const Tensor& t) { return (void*)c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
+inline void* cur_stream(const Tensor& t) {          // (a CPU tensor is refused here, before anything touches HIP)
+    TORCH_CHECK(t.is_cuda(), "veloxseg_amd: tensor is on ", t.device(), "; the VeloxSeg hot path runs only on an MI355X (HIP kernels, no CPU fallback)");
+    return (void*)c10::hip::getCurrentHIPStream(t.device().index()).stream();
+}
 
 struct ConvFn : public torch::autograd::Function<ConvFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& x, const OptT& x2, const Tensor& w, const OptT& b, int64_t K, int64_t S, int64_t P, int64_t G, int64_t ps) {
@@ -885,7 +893,7 @@ struct PwaCoreFn : public torch::autograd::Function<PwaCoreFn> {
 
 // ------------------------------------------------------------------------------------------------------------------- small single-kernel nodes
 // ConvTranspose3d(k=2, s=2) (conv_blocks.py:29-35), PatchMerging's space-to-depth (attention_utils.py:144-159), F.interpolate(trilinear, align_corners)
-// (VeloxSeg.py:183) and the SDKT Gram matrix (loss.py:39-60) as C++ nodes: the same C-ABI calls as the python nodes of functional.py.
+// (VeloxSeg.py:183) and the SDKT Gram matrix (loss.py:39-60).
 struct UpconvFn : public torch::autograd::Function<UpconvFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& x_in, const Tensor& w, const OptT& b_, bool feeds_in) {
         check_in(x_in, "conv_transpose3d");
@@ -913,7 +921,7 @@ struct UpconvFn : public torch::autograd::Function<UpconvFn> {
         if (dw || db)
             wgrad_submit(s_, x.device().index(), [=](void* s) {     // the transposed conv's weight gradient = the stride-2 conv's with x and dy swapped
                 if (dw && F.upconv_wgrad_mfma && vx_upconv_k2s2_wgrad_ok(Ci, Co)) VX(vx_upconv_k2s2_wgrad, fp(x), fp(dy), dw, B, Ci, Co, d, h, wd, s);
-                else if (dw) VX(vx_conv3d_bwd_weight_tiled, fp(dy), nullptr, 0, fp(x), dw, nullptr, B, Co, 2 * d, 2 * h, 2 * wd, Ci, 2, 2, 0, 1, 1, s);
+                else if (dw) conv_wgrad_generic(fp(dy), nullptr, 0, fp(x), dw, nullptr, B, Co, 2 * d, 2 * h, 2 * wd, Ci, 2, 2, 0, 1, 1, s);
                 if (db) VX(vx_channel_sum, fp(dy), db, B, Co, 8L * d * h * wd, s);
             });
         if (!WG.enabled) WG.done.clear();
@@ -993,10 +1001,8 @@ static int jlc_img_kind(int C, int G, int D, int H, int W) {
     if (vx_jlc_cl_ok(C, G, D, H, W)) return 2;
     return 0;
 }
-static std::pair<Tensor, std::shared_ptr<JLCState>> jlc_fwd_f(const Tensor& x, const std::vector<Tensor>& ws, const std::vector<Tensor>& bs, int G, const Tensor& l1w, const Tensor& l1b, const Tensor& l2w,
-                        const Tensor& l2b, double p, int64_t site, int64_t rs, int64_t stream) {
-        auto st = std::make_shared<JLCState>();
-        void* s_ = sp(stream);
+static Tensor jlc_fwd_f(JLCState* st, const Tensor& x, const std::vector<Tensor>& ws, const std::vector<Tensor>& bs, int G, const Tensor& l1w, const Tensor& l1b, const Tensor& l2w,
+                        const Tensor& l2b, double p, int64_t site, int64_t rs, void* s_) {
         const int n = (int)ws.size();
         if (F.fuse_blocks && n == 3 && x.dim() == 5 && ws[0].size(2) == 1 && ws[1].size(2) == 3 && ws[2].size(2) == 5) {
             const int B = x.size(0), C = x.size(1), D = x.size(2), H = x.size(3), W = x.size(4), R = l1w.size(0);
@@ -1063,7 +1069,7 @@ static std::pair<Tensor, std::shared_ptr<JLCState>> jlc_fwd_f(const Tensor& x, c
                 else
                 VX(vx_mlp_fwd_h, (const void*)f.o.data_ptr(), 0, part_o.data_ptr<double>(), f.nch, mp(f.stats_o), nullptr, nullptr, fp(l1w), fp(l1b), fp(l2w), fp(l2b), mp(out), B, C, R, V,
                                (float)F.in_eps, f.rs, 0ull, 0.0f, (unsigned long long)site, (float)p, (int)f.h16, s_);
-                return {out, st};
+                return out;
             }
         }
         st->convs.resize(n);
@@ -1087,11 +1093,11 @@ static std::pair<Tensor, std::shared_ptr<JLCState>> jlc_fwd_f(const Tensor& x, c
             Tensor z = conv_fwd_impl(st->c2, h, Tensor(), l2w, l2b, 1, 1, 0, 1, 1, true, s_);
             out = axpy_fwd_impl(st->r, o, z, 1.0, p, site, sp(rs), s_);
         }
-        return {out, st};
+        return out;
     }
 
-static Tensor jlc_bwd_f(std::shared_ptr<JLCState> st, const Tensor& dout_in, bool need_x, int64_t stream) {
-        void* s_ = sp(stream);
+// (the node drops the state -- saved activations included -- when this returns)
+static Tensor jlc_bwd_f(JLCState* st, const Tensor& dout_in, bool need_x, void* s_) {
         if (st->blk) {
             JLCFusedState& f = st->f;
             Tensor dout = contig(dout_in);
@@ -1167,14 +1173,13 @@ static Tensor jlc_bwd_f(std::shared_ptr<JLCState> st, const Tensor& dout_in, boo
                     }
                     if (dw1) {
                         if (g1fast) VX(vx_gconv1_bwd_weight, fp(xk), gq, dw1, nullptr, B, C, G, V, s);
-                        else VX(vx_conv3d_bwd_weight_tiled, fp(xk), nullptr, 0, gq, dw1, nullptr, B, C, D, H, W, C, 1, 1, 0, G, 1, s);
+                        else conv_wgrad_generic(fp(xk), nullptr, 0, gq, dw1, nullptr, B, C, D, H, W, C, 1, 1, 0, G, 1, s);
                     }
-                    if (dw3) VX(vx_conv3d_bwd_weight_tiled, fp(xk), nullptr, 0, gq + n1, dw3, nullptr, B, C, D, H, W, C, 3, 1, 1, G, 1, s);
-                    if (dw5) VX(vx_conv3d_bwd_weight_tiled, fp(xk), nullptr, 0, gq + 2 * n1, dw5, nullptr, B, C, D, H, W, C, 5, 1, 2, G, 1, s);
+                    if (dw3) conv_wgrad_generic(fp(xk), nullptr, 0, gq + n1, dw3, nullptr, B, C, D, H, W, C, 3, 1, 1, G, 1, s);
+                    if (dw5) conv_wgrad_generic(fp(xk), nullptr, 0, gq + 2 * n1, dw5, nullptr, B, C, D, H, W, C, 5, 1, 2, G, 1, s);
                 });
                 if (!WG.enabled) WG.done.clear();
             }
-            st.reset();
             return dx;
         }
         const Tensor& dout = dout_in;
@@ -1204,15 +1209,12 @@ static Tensor jlc_bwd_f(std::shared_ptr<JLCState> st, const Tensor& dout_in, boo
             if (F.skip_in_bias) grad_ptr(st->convs[k].b);         // the (zero) gradient tensor still exists for optimizers that walk p.grad
             conv_bwd_impl(st->convs[k], g[k], true, t1, t2, s_, d_o, /*skip_bias=*/F.skip_in_bias);
         }
-        st.reset();
         if (!need_x) return Tensor();
         return d_o;
     }
 
-static std::pair<Tensor, std::shared_ptr<FFNState>> ffn_fwd_f(const Tensor& y, const Tensor& gamma, const Tensor& beta, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, double p,
-                        int64_t site1, int64_t site2, int64_t rs, int64_t stream) {
-        auto st = std::make_shared<FFNState>();
-        void* s_ = sp(stream);
+static Tensor ffn_fwd_f(FFNState* st, const Tensor& y, const Tensor& gamma, const Tensor& beta, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, double p,
+                        int64_t site1, int64_t site2, int64_t rs, void* s_) {
         if (F.fuse_blocks && y.dim() == 5) {
             const int B = y.size(0), C = y.size(1), R = w1.size(0);
             const long V = y.numel() / ((long)B * C);
@@ -1224,7 +1226,7 @@ static std::pair<Tensor, std::shared_ptr<FFNState>> ffn_fwd_f(const Tensor& y, c
                 Tensor out = at::empty_like(st->y);
                 VX(vx_mlp_fwd, fp(st->y), 1, nullptr, 0, nullptr, fp(gamma), fp(beta), fp(w1), fp(b1), fp(w2), fp(b2), mp(out), B, C, R, V, (float)F.ln_eps, st->rs,
                                (unsigned long long)site1, (float)p, (unsigned long long)site2, (float)p, s_);
-                return {out, st};
+                return out;
             }
         }
         Tensor n = ln_fwd_impl(st->ln, y, gamma, beta, s_);
@@ -1241,11 +1243,10 @@ static std::pair<Tensor, std::shared_ptr<FFNState>> ffn_fwd_f(const Tensor& y, c
             Tensor z = conv_fwd_impl(st->c2, h, Tensor(), w2, b2, 1, 1, 0, 1, 1, true, s_);
             out = axpy_fwd_impl(st->r, y, z, 1.0, p, site2, sp(rs), s_);
         }
-        return {out, st};
+        return out;
     }
 
-static Tensor ffn_bwd_f(std::shared_ptr<FFNState> st, const Tensor& dout_in, int64_t stream) {
-        void* s_ = sp(stream);
+static Tensor ffn_bwd_f(FFNState* st, const Tensor& dout_in, void* s_) {
         if (st->blk) {
             Tensor dout = contig(dout_in);
             const int B = st->y.size(0), C = st->y.size(1), R = st->w1.size(0);
@@ -1279,14 +1280,12 @@ struct JLCFn : public torch::autograd::Function<JLCFn> {
         std::vector<Tensor> ws{w0}, bs{b0};
         if (w1.has_value() && w1->defined()) { ws.push_back(*w1); bs.push_back(b1.value()); }
         if (w2.has_value() && w2->defined()) { ws.push_back(*w2); bs.push_back(b2.value()); }
-        auto r = jlc_fwd_f(x, ws, bs, (int)G, l1w, l1b, l2w, l2b, p, site, rs, (int64_t)cur_stream(x));
-        put_state<std::shared_ptr<JLCState>>(ctx)->s = r.second;
+        auto h = put_state<JLCState>(ctx);
         ctx->saved_data["rng"] = take_rng_keep();
-        return r.first;
+        return jlc_fwd_f(&h->s, x, ws, bs, (int)G, l1w, l1b, l2w, l2b, p, site, rs, cur_stream(x));
     }
     static variable_list backward(AutogradContext* ctx, variable_list g) {
-        auto st = get_state<std::shared_ptr<JLCState>>(ctx);
-        Tensor dx = jlc_bwd_f(st, g[0], ctx->needs_input_grad(0), (int64_t)cur_stream(g[0]));
+        Tensor dx = jlc_bwd_f(&get_state<JLCState>(ctx), g[0], ctx->needs_input_grad(0), cur_stream(g[0]));
         ctx->saved_data.clear();
         variable_list out(15);
         out[0] = dx;
@@ -1296,14 +1295,12 @@ struct JLCFn : public torch::autograd::Function<JLCFn> {
 struct FFNFn : public torch::autograd::Function<FFNFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& y, const Tensor& gamma, const Tensor& beta, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2,
                           double p, int64_t site1, int64_t site2, int64_t rs) {
-        auto r = ffn_fwd_f(y, gamma, beta, w1, b1, w2, b2, p, site1, site2, rs, (int64_t)cur_stream(y));
-        put_state<std::shared_ptr<FFNState>>(ctx)->s = r.second;
+        auto h = put_state<FFNState>(ctx);
         ctx->saved_data["rng"] = take_rng_keep();
-        return r.first;
+        return ffn_fwd_f(&h->s, y, gamma, beta, w1, b1, w2, b2, p, site1, site2, rs, cur_stream(y));
     }
     static variable_list backward(AutogradContext* ctx, variable_list g) {
-        auto st = get_state<std::shared_ptr<FFNState>>(ctx);
-        Tensor dy = ffn_bwd_f(st, g[0], (int64_t)cur_stream(g[0]));
+        Tensor dy = ffn_bwd_f(&get_state<FFNState>(ctx), g[0], cur_stream(g[0]));
         ctx->saved_data.clear();
         variable_list out(11);
         out[0] = dy;
@@ -1609,22 +1606,16 @@ VX_OP_IMPLS(CPU, _cpu)
 #undef VX_OP_IMPLS
 
 PYBIND11_MODULE(_vxops, m) {
-    m.doc() = "C++ operator bodies of veloxseg_amd.functional (same C-ABI calls, no interpreter in between)";
-    py::class_<ConvState, std::shared_ptr<ConvState>>(m, "ConvState");
-    py::class_<INState, std::shared_ptr<INState>>(m, "INState");
-    py::class_<LNState, std::shared_ptr<LNState>>(m, "LNState");
-    py::class_<GeluState, std::shared_ptr<GeluState>>(m, "GeluState");
-    py::class_<AxpyState, std::shared_ptr<AxpyState>>(m, "AxpyState");
-    py::class_<JLCState, std::shared_ptr<JLCState>>(m, "JLCState");
-    py::class_<FFNState, std::shared_ptr<FFNState>>(m, "FFNState");
-
+    m.doc() = "the host side of the VeloxSeg hot-path operators: C++ autograd nodes over the C ABI of libveloxseg_hip.so";
+    // the host-side kernel choices of functional.set_host_flags (+ the two epsilons); wgrad_untiled: the generic weight gradient on the untiled reference kernel
     m.def("set_flags", [](bool s1, bool expand_mfma, bool gconv1, bool wgrad_ws, bool patchify, bool in_row, int64_t pw_mfma_max_v, int64_t in_row_max, double in_eps,
-                          double ln_eps) {
+                          double ln_eps, bool wgrad_untiled) {
         F.use_s1 = s1; F.use_expand_mfma = expand_mfma; F.use_gconv1 = gconv1; F.use_wgrad_ws = wgrad_ws; F.use_patchify = patchify; F.use_in_row = in_row;
-        F.pw_mfma_max_v = pw_mfma_max_v; F.in_row_max = in_row_max; F.in_eps = in_eps; F.ln_eps = ln_eps;
-    });
+        F.pw_mfma_max_v = pw_mfma_max_v; F.in_row_max = in_row_max; F.in_eps = in_eps; F.ln_eps = ln_eps; F.wgrad_untiled = wgrad_untiled;
+    }, py::arg("s1"), py::arg("expand_mfma"), py::arg("gconv1"), py::arg("wgrad_ws"), py::arg("patchify"), py::arg("in_row"), py::arg("pw_mfma_max_v"), py::arg("in_row_max"),
+       py::arg("in_eps"), py::arg("ln_eps"), py::arg("wgrad_untiled") = false);
 
-    // C++ autograd nodes: return tensors that already carry their grad_fn
+    // the autograd nodes: return tensors that already carry their grad_fn
     m.def("conv", [](const Tensor& x, const OptT& x2, const Tensor& w, const OptT& b, int64_t K, int64_t S, int64_t P, int64_t G, int64_t ps) {
         return ConvFn::apply(x, x2, w, b, K, S, P, G, ps);
     });
@@ -1775,71 +1766,4 @@ PYBIND11_MODULE(_vxops, m) {
     m.def("set_fuse_res", [](bool on) { F.fuse_res = on; });           // A/B: residual + dropout in the epilogue of the second 1x1 conv of the JLC / FFN stage
     m.def("set_in_split2", [](bool on) { F.in_split2 = on; });         // A/B: long-row InstanceNorm in 2 launches per direction (0 = separate stats / finalise / apply launches)
     m.def("set_skip_in_bias", [](bool on) { F.skip_in_bias = on; });   // A/B: 0 = compute the (mathematically zero) bias gradients of convs that feed an InstanceNorm
-
-    m.def("conv_fwd", [](const Tensor& x, const OptT& x2, const Tensor& w, const OptT& b, int K, int S, int P, int G, int ps, int64_t stream) {
-        auto st = std::make_shared<ConvState>();
-        Tensor y = conv_fwd_impl(*st, x, x2.value_or(Tensor()), w, b.value_or(Tensor()), K, S, P, G, ps, x.requires_grad(), sp(stream));
-        return py::make_tuple(y, st);
-    });
-    m.def("conv_bwd", [](std::shared_ptr<ConvState> st, const Tensor& dy, bool need_x, int64_t stream) {
-        Tensor dx, dx2;
-        conv_bwd_impl(*st, dy, need_x, dx, dx2, sp(stream));
-        return py::make_tuple(dx.defined() ? py::cast(dx) : py::none(), dx2.defined() ? py::cast(dx2) : py::none());
-    });
-
-    m.def("in_fwd", [](const OptT& res, bool act, const std::vector<Tensor>& ys, int64_t stream) {
-        auto st = std::make_shared<INState>();
-        Tensor out = in_fwd_impl(*st, res.value_or(Tensor()), act, ys, sp(stream));
-        return py::make_tuple(out, st);
-    });
-    m.def("in_bwd", [](std::shared_ptr<INState> st, const Tensor& dout, const std::vector<bool>& need, int64_t stream) {
-        auto g = in_bwd_impl(*st, dout, need, sp(stream));
-        py::list out;
-        for (auto& t : g) out.append(t.defined() ? py::cast(t) : py::none());
-        return out;
-    });
-
-    m.def("ln_fwd", [](const Tensor& x, const Tensor& g, const Tensor& bt, int64_t stream) {
-        auto st = std::make_shared<LNState>();
-        Tensor out = ln_fwd_impl(*st, x, g, bt, sp(stream));
-        return py::make_tuple(out, st);
-    });
-    m.def("ln_bwd", [](std::shared_ptr<LNState> st, const Tensor& dout, int64_t stream) { return ln_bwd_impl(*st, dout, sp(stream)); });
-
-    m.def("gelu_fwd", [](const Tensor& a, double p, int64_t site, int64_t rs, int64_t stream) {
-        auto st = std::make_shared<GeluState>();
-        Tensor h = gelu_fwd_impl(*st, a, p, site, sp(rs), sp(stream));
-        return py::make_tuple(h, st);
-    });
-    m.def("gelu_bwd", [](std::shared_ptr<GeluState> st, const Tensor& dh, int64_t stream) { return gelu_bwd_impl(*st, dh, sp(stream)); });
-
-    m.def("axpy_fwd", [](const OptT& x, const Tensor& z, double alpha, double p, int64_t site, int64_t rs, int64_t stream) {
-        auto st = std::make_shared<AxpyState>();
-        Tensor out = axpy_fwd_impl(*st, x.value_or(Tensor()), z, alpha, p, site, sp(rs), sp(stream));
-        return py::make_tuple(out, st);
-    });
-    m.def("axpy_bwd", [](std::shared_ptr<AxpyState> st, const Tensor& dout, bool need_x, int64_t stream) {
-        Tensor dx, dz;
-        axpy_bwd_impl(*st, dout, need_x, dx, dz, sp(stream));
-        return py::make_tuple(dx.defined() ? py::cast(dx) : py::none(), dz);
-    });
-
-    // JLC block: ws/bs = the spatial convs' weights / biases (kernel sizes from the weight shapes), groups G; l1/l2 = the channel MLP
-    m.def("jlc_fwd", [](const Tensor& x, const std::vector<Tensor>& ws, const std::vector<Tensor>& bs, int G, const Tensor& l1w, const Tensor& l1b, const Tensor& l2w,
-                        const Tensor& l2b, double p, int64_t site, int64_t rs, int64_t stream) {
-        auto r = jlc_fwd_f(x, ws, bs, G, l1w, l1b, l2w, l2b, p, site, rs, stream);
-        return py::make_tuple(r.first, r.second);
-    });
-    m.def("jlc_bwd", [](std::shared_ptr<JLCState> st, const Tensor& dout, bool need_x, int64_t stream) -> py::object {
-        Tensor d = jlc_bwd_f(st, dout, need_x, stream);
-        return d.defined() ? py::cast(d) : py::none();
-    });
-
-    // FFN tail: out = y + Drop(linear2(Drop(GELU(linear1(LN(y))))))
-    m.def("ffn_fwd", [](const Tensor& y, const Tensor& gamma, const Tensor& beta, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, double p,
-                        int64_t site1, int64_t site2, int64_t rs, int64_t stream) {
-        auto r = ffn_fwd_f(y, gamma, beta, w1, b1, w2, b2, p, site1, site2, rs, stream);
-        return py::make_tuple(r.first, r.second);
-    });
-    m.def("ffn_bwd", [](std::shared_ptr<FFNState> st, const Tensor& dout, int64_t stream) { return ffn_bwd_f(st, dout, stream); });
 }

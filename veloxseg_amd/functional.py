@@ -6,6 +6,10 @@ ACCUMULATED IN PLACE into `param.grad` by the weight-gradient kernels (float ato
 returned to autograd for them: no per-parameter AccumulateGrad kernels, one flat gradient buffer for
 the RCCL all-reduce and the fused AdamW (see veloxseg_amd/engine.py).
 
+The host side of the convolutions, norms, element-wise operators and composite blocks -- kernel selection, workspaces, autograd nodes -- is C++
+(csrc/_vxops.cpp); the functions here call those nodes directly or through torch.ops.veloxseg.*.  The fused PWA chains, the fan-out and the loss
+are Python autograd functions over the same C ABI.
+
 There is no CPU implementation here on purpose (tier rule: the product path has no fallback).
 """
 from __future__ import annotations
@@ -18,7 +22,8 @@ import torch
 
 from . import _hip as H
 
-WGRAD_ENTRY = "vx_conv3d_bwd_weight_tiled"    # "vx_conv3d_bwd_weight" = untiled reference kernel (kept for A/B tests)
+# host-side kernel choices of the C++ operator bodies (csrc/_vxops.cpp `Flags`); change them with set_host_flags(), which forwards them
+WGRAD_UNTILED = False                         # generic weight gradient on the untiled reference kernel vx_conv3d_bwd_weight (A/B tests) instead of the tiled one
 USE_EXPAND_MFMA = True                        # patch-expand input gradient on fp32 MFMA (False = conv_s1 VALU kernel)
 # fp32 mode of the patch-expand layers (forward + input gradient, 49 % of the training FLOPs): 3 = every fp32 operand as three bf16 pieces, six bf16 MFMAs per
 # pair (the fp32 product to 2^-27; 2.7 x fewer matrix-pipe clocks than v_mfma_f32_16x16x4_f32), 2 = two pieces / three MFMAs (~1e-5 relative), 0 = fp32 MFMA
@@ -27,7 +32,6 @@ USE_S1 = True                                 # register-blocked stride-1 conv k
 USE_IN_ROW = True                             # InstanceNorm of short rows (V <= 4096): statistics + application in one launch
 IN_ROW_MAX = 4096
 USE_WGRAD_WS = False                          # tiled weight gradient through a partial-sum workspace (deterministic order) instead of float atomics (30 fewer launches per step: +2 %)
-_wgrad_ws = {}
 USE_PATCHIFY = True                           # kernel == stride convs (PatchEmbed) as patchify + 1x1 conv (False = generic direct conv)
 USE_LOSS_BWD4 = True                          # loss backward of all deep-supervision heads in one launch (False = one launch per head)
 USE_GCONV1 = True                             # dedicated weight-gradient kernel of the 1x1x1 grouped JLC conv (False = tiled kernel)
@@ -200,33 +204,50 @@ def grad_buf(p: torch.Tensor) -> torch.Tensor:
     return p.grad
 
 
-USE_CPP = True                                # operator bodies in C++ (veloxseg_amd._vxops) instead of the python code below; same C-ABI calls
-_CPP = [False, None]
-_CPP_DEFAULTS = None
+_HOST_FLAGS = ("USE_S1", "USE_EXPAND_MFMA", "USE_GCONV1", "USE_WGRAD_WS", "USE_PATCHIFY", "USE_IN_ROW", "PW_MFMA_MAX_V", "IN_ROW_MAX", "WGRAD_UNTILED")
+_CPP = None
+
+
+def _push_host_flags(m):
+    m.set_flags(s1=USE_S1, expand_mfma=USE_EXPAND_MFMA, gconv1=USE_GCONV1, wgrad_ws=USE_WGRAD_WS, patchify=USE_PATCHIFY, in_row=USE_IN_ROW,
+                pw_mfma_max_v=PW_MFMA_MAX_V, in_row_max=IN_ROW_MAX, in_eps=IN_EPS, ln_eps=LN_EPS, wgrad_untiled=WGRAD_UNTILED)
 
 
 def cpp_module(reload: bool = False):
-    """veloxseg_amd._vxops (csrc/_vxops.cpp, built by __graft_entry__.build); None only when VELOXSEG_NO_CPP=1 selects the python operator bodies
-    (same kernels) on purpose; a module that is missing or does not import raises"""
-    if reload:
-        _CPP[0] = False
-    if not _CPP[0]:
-        _CPP[0] = True
-        if os.environ.get("VELOXSEG_NO_CPP") != "1":
-            try:
-                H.LIB.load()
-                from . import _vxops
-                _vxops.set_expand_split(EXPAND_SPLIT)
-                _vxops.set_tile_min_c(TILE_MIN_C)
-                _vxops.set_flags(USE_S1, USE_EXPAND_MFMA, USE_GCONV1, USE_WGRAD_WS, USE_PATCHIFY, USE_IN_ROW, PW_MFMA_MAX_V, IN_ROW_MAX, IN_EPS, LN_EPS)
-                _CPP[1] = _vxops
-            except ImportError as e:
-                # the C++ operator path IS the product path; the python bodies below are its A/B twin and are only taken when asked for
-                # (VELOXSEG_NO_CPP=1).  A build that lost _vxops must not silently change which host code runs.
-                raise RuntimeError("veloxseg_amd: the C++ operator module veloxseg_amd._vxops cannot be imported (" + str(e)[:200] + "); build it with "
-                                   "`python -c 'import __graft_entry__ as g; g.build()'`, or set VELOXSEG_NO_CPP=1 to run the python operator bodies "
-                                   "(same HIP kernels) on purpose") from e
-    return _CPP[1]
+    """veloxseg_amd._vxops (csrc/_vxops.cpp, built by __graft_entry__.build): the host side of the operators and the owner of the torch.ops.veloxseg
+    schemas, configured with this module's flags when it is first loaded; a module that is missing or does not import raises"""
+    global _CPP
+    if _CPP is None or reload:
+        try:
+            H.LIB.load()
+            from . import _vxops
+        except ImportError as e:
+            raise RuntimeError("veloxseg_amd: the C++ operator module veloxseg_amd._vxops cannot be imported (" + str(e)[:200] + "); build it with "
+                               "`python -c 'import __graft_entry__ as g; g.build()'`") from e
+        _vxops.set_expand_split(EXPAND_SPLIT)
+        _vxops.set_tile_min_c(TILE_MIN_C)
+        _push_host_flags(_vxops)
+        _CPP = _vxops
+    return _CPP
+
+
+def set_host_flags(**kw):
+    """Set kernel-choice flags (the names of _HOST_FLAGS) here AND in the C++ operator bodies, which make the choice; returns the previous
+    values of the flags it was given, so that `old = set_host_flags(...)` / `finally: set_host_flags(**old)` restores them."""
+    unknown = sorted(set(kw) - set(_HOST_FLAGS))
+    if unknown:
+        raise TypeError(f"set_host_flags: unknown flag(s) {unknown}; known: {_HOST_FLAGS}")
+    g = globals()
+    old = {k: g[k] for k in kw}
+    g.update(kw)
+    _push_host_flags(cpp_module())
+    return old
+
+
+def _ops():
+    """torch.ops.veloxseg, with the extension that registers it loaded"""
+    cpp_module()
+    return torch.ops.veloxseg
 
 
 _PRECISION = "fp32"
@@ -241,10 +262,6 @@ def set_precision(mode: str):
     if mode not in ("fp32", "bf16"):
         raise ValueError("precision must be 'fp32' or 'bf16'")
     m = cpp_module()
-    if m is None:
-        if mode == "bf16":
-            raise RuntimeError("veloxseg_amd: the bf16 mode lives in the C++ operator path (veloxseg_amd._vxops), which is not built / enabled")
-        return
     m.set_bf16_expand(mode == "bf16")
     # round 6: the bf16 mode also STORES 16-bit tensors (VELOXSEG_BF16_STORAGE=0: operands only, the mode of rounds 2-5, for the A/B): the block-internal tensors of the JLC blocks
     # at the 32^3 level (y_k, o, dn, d_o, g_k) and the full-resolution heads / reconstructions with their gradients; fp32: statistics, sums, soft-max, loss, master weights,
@@ -262,38 +279,8 @@ def get_precision() -> str:
     return _PRECISION
 
 
-def _flag_tuple():
-    return (WGRAD_ENTRY, USE_S1, USE_EXPAND_MFMA, USE_GCONV1, USE_WGRAD_WS, USE_PATCHIFY, USE_IN_ROW, PW_MFMA_MAX_V, IN_ROW_MAX)
-
-
-def cpp_node(name):
-    """the C++ module when single operators may run as C++ autograd nodes (model code that builds multi-operator nodes asks here), else None"""
-    return _cpp()
-
-
 def rs_ptr(device, p):
-    return _rs_ptr(device, p)
-
-
-def _cpp():
-    """the C++ module when it may be used: built, enabled, and every A/B flag at the default it was configured with (tests that flip a
-    flag run the python bodies)"""
-    global _CPP_DEFAULTS
-    if not USE_CPP:
-        return None
-    m = _CPP[1] if _CPP[0] else cpp_module()
-    if m is None:
-        return None
-    if _CPP_DEFAULTS is None:
-        _CPP_DEFAULTS = _flag_tuple()
-    return m if _flag_tuple() == _CPP_DEFAULTS else None
-
-
-def _cpp_mod():
-    return _CPP[1]
-
-
-def _rs_ptr(device, p):
+    """address of the {seed, step} tensor for the C++ nodes (0 without dropout)"""
     return rng_state(device).data_ptr() if p > 0 else 0
 
 
@@ -315,130 +302,6 @@ def _check(x: torch.Tensor, what: str):
 # ------------------------------------------------------------------------------------------------
 # convolutions
 # ------------------------------------------------------------------------------------------------
-class _Conv3dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, x2, w, b, K, S, P, G, ps):
-        m = _cpp() if x.is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            y, ctx.cst = m.conv_fwd(x, x2, w, b, K, S, P, G, ps, H.stream_ptr())
-            return y
-        _check(x, "conv3d")
-        x = _c(x)
-        x2 = _c(x2) if x2 is not None else None
-        B, C1, D, Hh, W = x.shape
-        Cin = C1 + (x2.shape[1] if x2 is not None else 0)
-        Cout = w.shape[0]
-        assert w.shape[1] * G == Cin and w.shape[2] == K, (tuple(w.shape), Cin, G, K)
-        Do, Ho, Wo = (D + 2 * P - K) // S + 1, (Hh + 2 * P - K) // S + 1, (W + 2 * P - K) // S + 1
-        if ps == 1:
-            y = torch.empty((B, Cout, Do, Ho, Wo), device=x.device, dtype=torch.float32)
-        else:
-            y = torch.empty((B, Cout // ps ** 3, Do * ps, Ho * ps, Wo * ps), device=x.device, dtype=torch.float32)
-        pw = (K == 1 and S == 1 and P == 0 and G == 1 and ps == 1 and Cin % 4 == 0 and C1 % 4 == 0)
-        s1 = (x2 is None and S == 1 and K in (3, 5) and P == K // 2 and (Cout // G) % 4 == 0 and (Cin // G) % 4 == 0 and USE_S1)
-        ctx.s1 = s1
-        # kernel == stride, no padding, input needs no gradient (PatchEmbed on the image): patchify once, then it is a 1x1 conv
-        patch = (USE_PATCHIFY and K == S and K in (2, 4) and P == 0 and G == 1 and ps == 1 and x2 is None and not x.requires_grad
-                 and D % K == 0 and Hh % K == 0 and W % K == 0 and (Cin * K ** 3) % 4 == 0)
-        ctx.patch = patch
-        if patch:
-            Ck, Vo = Cin * K ** 3, Do * Ho * Wo
-            xs = torch.empty((B, Ck, Do, Ho, Wo), device=x.device, dtype=torch.float32)
-            st = H.stream_ptr()
-            H.call("vx_patchify", H.P(x), H.P(xs), B, Cin, Do, Ho, Wo, K, st)
-            if Vo <= PW_MFMA_MAX_V:
-                H.call("vx_pw_conv_mfma", H.P(xs), None, Ck, H.P(w), 0, H.P(b), H.P(y), None, 0, B, Cout, Ck, Ck, Vo, 0, st)
-            else:
-                H.call("vx_pw_conv_fwd", H.P(xs), None, Ck, H.P(w), H.P(b), H.P(y), B, Ck, Cout, Vo, st)
-            ctx.save_for_backward(xs, None)
-            ctx.w, ctx.b = w, b
-            ctx.meta = (B, C1, Cin, D, Hh, W, Cout, K, S, P, G, ps)
-            ctx.pw = False
-            return y
-        if pw and D * Hh * W <= PW_MFMA_MAX_V:
-            H.call("vx_pw_conv_mfma", H.P(x), H.P(x2), C1, H.P(w), 0, H.P(b), H.P(y), None, 0, B, Cout, Cin, Cin, D * Hh * W, 0, H.stream_ptr())
-        elif pw:
-            H.call("vx_pw_conv_fwd", H.P(x), H.P(x2), C1, H.P(w), H.P(b), H.P(y), B, Cin, Cout, D * Hh * W, H.stream_ptr())
-        elif s1:
-            rc = 1
-            if ps == 4 and K == 3 and Cin == 16 and G == 1 and Cout % 64 == 0 and USE_EXPAND_MFMA:      # patch-expand layer: MFMA tiles over an LDS halo
-                wt = torch.empty((Cout * 16 * 27,), device=x.device, dtype=torch.float32)
-                rc = H.query("vx_expand_fwd_mfma", H.P(x), H.P(w), H.P(b), H.P(wt), H.P(y), B, Cout // 64, D, Hh, W, H.stream_ptr())
-            if rc == 1:
-                H.call("vx_conv_s1", H.P(x), H.P(w), H.P(b), H.P(y), B, Cin, Cout, D, Hh, W, K, G, 0, 1, ps, 0, H.stream_ptr())
-        else:
-            H.call("vx_conv3d_fwd", H.P(x), H.P(x2), C1, H.P(w), H.P(b), H.P(y), B, Cin, D, Hh, W, Cout, K, S, P, G, ps, H.stream_ptr())
-        ctx.pw = pw
-        ctx.save_for_backward(x, x2)
-        ctx.w, ctx.b = w, b
-        ctx.meta = (B, C1, Cin, D, Hh, W, Cout, K, S, P, G, ps)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        if ctx.cst is not None:
-            dx, dx2 = _cpp_mod().conv_bwd(ctx.cst, dy, bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]), H.stream_ptr())
-            ctx.cst = None
-            return dx, dx2, None, None, None, None, None, None, None
-        x, x2 = ctx.saved_tensors
-        w, b = ctx.w, ctx.b
-        B, C1, Cin, D, Hh, W, Cout, K, S, P, G, ps = ctx.meta
-        dy = _c(dy)
-        st = H.stream_ptr()
-        if ctx.patch:                           # x is the patchified input (B, Cin*K^3, Do, Ho, Wo); the image itself needs no gradient
-            if w.requires_grad:
-                db = grad_buf(b) if (b is not None and b.requires_grad) else None
-                H.call("vx_pw_conv_bwd_weight", H.P(x), None, Cin * K ** 3, H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cin * K ** 3, Cout,
-                       (D // K) * (Hh // K) * (W // K), st)
-            return None, None, None, None, None, None, None, None, None
-        dx = dx2 = None
-        need_x = ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1])
-        if need_x:
-            dx = torch.empty_like(x)
-            dx2 = torch.empty_like(x2) if x2 is not None else None
-            if ctx.pw and D * Hh * W <= PW_MFMA_MAX_V:
-                H.call("vx_pw_conv_mfma", H.P(dy), None, 0, H.P(w), 1, None, H.P(dx), H.P(dx2), C1, B, Cin, Cout, Cin, D * Hh * W, 0, st)
-            elif ctx.pw:
-                H.call("vx_pw_conv_bwd_data", H.P(dy), H.P(w), H.P(dx), H.P(dx2), C1, B, Cin, Cout, D * Hh * W, 0, st)
-            elif ctx.s1 and ps == 4 and K == 3 and Cin == 16 and G == 1 and USE_EXPAND_MFMA:
-                wt = torch.empty((Cout * 16 * 27,), device=x.device, dtype=torch.float32)
-                H.call("vx_expand_bwd_data_mfma", H.P(dy), H.P(w), H.P(wt), H.P(dx), B, Cout // 64, D, Hh, W, 0, st)
-            elif ctx.s1:
-                H.call("vx_conv_s1", H.P(dy), H.P(w), None, H.P(dx), B, Cout, Cin, D, Hh, W, K, G, 1, ps, 1, 0, st)
-            else:
-                H.call("vx_conv3d_bwd_data", H.P(dy), H.P(w), None, H.P(dx), H.P(dx2), C1, B, Cin, D, Hh, W, Cout, K, S, P, G, ps, 0, st)
-        if w.requires_grad:
-            db = grad_buf(b) if (b is not None and b.requires_grad) else None
-            if K == 1 and S == 1 and P == 0 and G == 1 and ps == 1:
-                H.call("vx_pw_conv_bwd_weight", H.P(x), H.P(x2), C1, H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cin, Cout, D * Hh * W, st)
-            elif (USE_GCONV1 and K == 1 and S == 1 and P == 0 and G > 1 and ps == 1 and x2 is None and Cin == Cout and (Cin // G) in (4, 8, 16)
-                  and (D * Hh * W) % 4 == 0):
-                H.call("vx_gconv1_bwd_weight", H.P(x), H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cin, G, D * Hh * W, st)
-            elif ctx.s1 and ps == 4 and K == 3 and Cin == 16 and G == 1 and USE_EXPAND_MFMA:
-                xcl = torch.empty((B * D * Hh * W * 16,), device=x.device, dtype=torch.float32)
-                H.call("vx_expand_wgrad_mfma", H.P(x), H.P(xcl), H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cout // 64, D, Hh, W, st)
-            elif (K == 7 and S == 4 and P == 3 and G == 1 and ps == 1 and x2 is None
-                  and H.query("vx_down_wgrad_ws_floats", B, Cin, D, Hh, W, Cout) > 0):
-                nws = H.query("vx_down_wgrad_ws_floats", B, Cin, D, Hh, W, Cout)
-                ws = torch.empty((nws,), device=x.device, dtype=torch.float32)
-                H.call("vx_down_wgrad_mfma", H.P(x), H.P(dy), H.P(grad_buf(w)), H.P(db), H.P(ws), nws, B, Cin, D, Hh, W, Cout, st)
-            elif (G == 1 and ps == 1 and S > 1 and x2 is None and WGRAD_ENTRY == "vx_conv3d_bwd_weight_tiled"
-                  and H.query("vx_conv_wgrad_gather_ok", B, Cin, D, Hh, W, Cout, K, S, P) == 1):
-                H.call("vx_conv_wgrad_gather_mfma", H.P(x), H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cin, D, Hh, W, Cout, K, S, P, st)
-            elif WGRAD_ENTRY == "vx_conv3d_bwd_weight_tiled" and USE_WGRAD_WS:
-                key = (B, Cin, D, Hh, W, Cout, K, S, P, G, ps)
-                nws = _wgrad_ws.get(key)
-                if nws is None:
-                    nws = _wgrad_ws[key] = H.query("vx_conv3d_bwd_weight_ws_floats", *key)
-                ws = torch.empty((nws,), device=x.device, dtype=torch.float32) if nws > 0 else None
-                H.call("vx_conv3d_bwd_weight_tiled_ws", H.P(x), H.P(x2), C1, H.P(dy), H.P(grad_buf(w)), H.P(db), H.P(ws), nws,
-                       B, Cin, D, Hh, W, Cout, K, S, P, G, ps, st)
-            else:
-                H.call(WGRAD_ENTRY, H.P(x), H.P(x2), C1, H.P(dy), H.P(grad_buf(w)), H.P(db), B, Cin, D, Hh, W, Cout, K, S, P, G, ps, st)
-        return dx, dx2, None, None, None, None, None, None, None
-
-
 # The model reaches the seven C++-registered operators THROUGH THE DISPATCHER (torch.ops.veloxseg.*: Autograd / CUDA / Meta keys registered by csrc/_vxops.cpp) wherever
 # the call has the schema's form; forms the schemas do not carry (two-pointer concat input, the "feeds an InstanceNorm" hint) call the node directly.  A taped step
 # replays captured launches, so the extra dispatcher hop costs the eager path only.
@@ -447,271 +310,46 @@ class _Conv3dFn(torch.autograd.Function):
 def conv3d(x, w, b=None, *, x2=None, stride=1, padding=0, groups=1, pixel_shuffle=1, out_bf16=False):
     """Conv3d (+ optional channel-concat input, + optional PixelShuffle store).  out_bf16 (bf16 storage mode, patch-expand layers only): the output is a bfloat16 tensor
     -- the full-resolution logits / reconstructions -- and the backward accepts a bfloat16 gradient; ignored wherever the 16-bit kernels do not apply."""
-    m = _cpp() if x.is_cuda else None
-    if out_bf16 and m is not None and x2 is None and _PRECISION == "bf16" and BF16_STORAGE:
-        return m.conv_h(x, w, b, int(w.shape[2]), int(stride), int(padding), int(groups), int(pixel_shuffle))
-    if m is not None and x2 is None:
-        return torch.ops.veloxseg.conv3d(x, w, b, int(stride), int(padding), int(groups), int(pixel_shuffle))
-    if m is not None:
-        return m.conv(x, x2, w, b, int(w.shape[2]), int(stride), int(padding), int(groups), int(pixel_shuffle))
-    return _Conv3dFn.apply(x, x2, w, b, int(w.shape[2]), int(stride), int(padding), int(groups), int(pixel_shuffle))
-
-
-class _ConvTransposeK2S2Fn(torch.autograd.Function):
-    """ConvTranspose3d(kernel=2, stride=2) run as the adjoint of a stride-2 conv (conv_blocks.py:29-35)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        _check(x, "conv_transpose3d")
-        x = _c(x)
-        B, Ci, d, h, wd = x.shape
-        Co = w.shape[1]
-        assert w.shape[0] == Ci and tuple(w.shape[2:]) == (2, 2, 2)
-        y = torch.empty((B, Co, 2 * d, 2 * h, 2 * wd), device=x.device, dtype=torch.float32)
-        H.call("vx_upconv_k2s2_fwd", H.P(x), H.P(w), H.P(b), H.P(y), B, Ci, Co, d, h, wd, H.stream_ptr())
-        ctx.save_for_backward(x)
-        ctx.w, ctx.b = w, b
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        w, b = ctx.w, ctx.b
-        dy = _c(dy)
-        B, Ci, d, h, wd = x.shape
-        Co = w.shape[1]
-        st = H.stream_ptr()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            H.call("vx_upconv_k2s2_bwd_data", H.P(dy), H.P(w), H.P(dx), B, Ci, Co, d, h, wd, st)
-        if w.requires_grad:
-            H.call(WGRAD_ENTRY, H.P(dy), None, 0, H.P(x), H.P(grad_buf(w)), None, B, Co, 2 * d, 2 * h, 2 * wd, Ci, 2, 2, 0, 1, 1, st)
-        if b is not None and b.requires_grad:
-            H.call("vx_channel_sum", H.P(dy), H.P(grad_buf(b)), B, Co, 8 * d * h * wd, st)
-        return dx, None, None
+    K = int(w.shape[2])
+    if x2 is not None:
+        return cpp_module().conv(x, x2, w, b, K, int(stride), int(padding), int(groups), int(pixel_shuffle))
+    if out_bf16 and _PRECISION == "bf16" and BF16_STORAGE:
+        return cpp_module().conv_h(x, w, b, K, int(stride), int(padding), int(groups), int(pixel_shuffle))
+    return _ops().conv3d(x, w, b, int(stride), int(padding), int(groups), int(pixel_shuffle))
 
 
 def conv_transpose_k2s2(x, w, b, feeds_instnorm: bool = False):
     """feeds_instnorm: the output goes straight into an InstanceNorm (UpConv): the bias gradient is zero by construction and is not computed"""
-    m = _cpp() if x.is_cuda else None
-    if m is not None and not feeds_instnorm and b is not None:
-        return torch.ops.veloxseg.conv_transpose_k2s2(x, w, b)
-    if m is not None:
-        return m.upconv_k2s2(x, w, b, bool(feeds_instnorm))
-    return _ConvTransposeK2S2Fn.apply(x, w, b)
+    if not feeds_instnorm and b is not None:
+        return _ops().conv_transpose_k2s2(x, w, b)
+    return cpp_module().upconv_k2s2(x, w, b, bool(feeds_instnorm))
 
 
 # ------------------------------------------------------------------------------------------------
 # InstanceNorm (+ activation, + n-way sum, + residual)
 # ------------------------------------------------------------------------------------------------
-class _InstNormSumFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, res, act, *ys):
-        m = _cpp() if ys[0].is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            out, ctx.cst = m.in_fwd(res, bool(act), list(ys), H.stream_ptr())
-            ctx.n, ctx.has_res = len(ys), res is not None
-            return out
-        n = len(ys)
-        assert 1 <= n <= 3
-        ys = [_c(y) for y in ys]
-        _check(ys[0], "instance_norm")
-        B, C = ys[0].shape[:2]
-        V = ys[0][0, 0].numel()
-        st = H.stream_ptr()
-        out = torch.empty_like(ys[0])
-        res_c = _c(res) if res is not None else None
-        pp = [H.P(y) for y in ys] + [None] * (3 - n)
-        if USE_IN_ROW and V <= IN_ROW_MAX:                      # short rows: statistics + application in one launch
-            sbuf = torch.empty((n, B * C * 2), device=ys[0].device, dtype=torch.float32)
-            stats = [sbuf[k] for k in range(n)]
-            ss = [H.P(s) for s in stats] + [None] * (3 - n)
-            H.call("vx_in_row_fwd", *pp, *ss, n, int(act), H.P(res_c), H.P(out), B * C, V, IN_EPS, st)
-        else:
-            stats = [torch.empty((B * C * 2,), device=ys[0].device, dtype=torch.float32) for _ in ys]
-            for y, s in zip(ys, stats):
-                part = torch.empty((B * C * 32,), device=y.device, dtype=torch.float64)
-                H.call("vx_in_stats", H.P(y), H.P(s), H.P(part, torch.float64), B * C, V, IN_EPS, st)
-            ss = [H.P(s) for s in stats] + [None] * (3 - n)
-            H.call("vx_in_apply_fwd", *pp, *ss, n, int(act), H.P(res_c), H.P(out), B * C, V, st)
-        ctx.save_for_backward(*ys, *stats)
-        ctx.n, ctx.act, ctx.has_res = n, int(act), res is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        n = ctx.n
-        if ctx.cst is not None:
-            grads = _cpp_mod().in_bwd(ctx.cst, dout, [bool(ctx.needs_input_grad[2 + k]) for k in range(n)], H.stream_ptr())
-            ctx.cst = None
-            dres = (dout if dout.is_contiguous() else dout.contiguous()) if (ctx.has_res and ctx.needs_input_grad[0]) else None
-            return (dres, None, *grads)
-        ys, stats = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
-        dout = _c(dout)
-        B, C = ys[0].shape[:2]
-        V = ys[0][0, 0].numel()
-        st = H.stream_ptr()
-        if USE_IN_ROW and V <= IN_ROW_MAX:
-            need = [bool(ctx.needs_input_grad[2 + k]) for k in range(n)]
-            grads = [torch.empty_like(ys[k]) if need[k] else None for k in range(n)]
-            if any(need):
-                H.call("vx_in_row_bwd", H.P(dout), *([H.P(y) for y in ys] + [None] * (3 - n)), *([H.P(s_) for s_ in stats] + [None] * (3 - n)),
-                       n, ctx.act, *([H.P(g) for g in grads] + [None] * (3 - n)), B * C, V, st)
-            dres = dout if (ctx.has_res and ctx.needs_input_grad[0]) else None
-            return (dres, None, *grads)
-        grads = []
-        for k in range(n):
-            if ctx.needs_input_grad[2 + k]:
-                dy = torch.empty_like(ys[k])
-                ws = torch.empty((B * C * 2,), device=dout.device, dtype=torch.float32)
-                part = torch.empty((B * C * 32,), device=dout.device, dtype=torch.float64)
-                H.call("vx_in_bwd", H.P(dout), H.P(ys[k]), H.P(stats[k]), ctx.act, H.P(ws), H.P(part, torch.float64), H.P(dy), B * C, V, st)
-                grads.append(dy)
-            else:
-                grads.append(None)
-        dres = dout if (ctx.has_res and ctx.needs_input_grad[0]) else None
-        return (dres, None, *grads)
-
-
 def instnorm_sum(ys: Sequence[torch.Tensor], act: bool = False, res: Optional[torch.Tensor] = None):
-    """(res) + sum_k act(InstanceNorm(y_k))."""
-    m = _cpp() if ys[0].is_cuda else None
-    if m is not None and 1 <= len(ys) <= 3:
-        return torch.ops.veloxseg.instance_norm_sum(list(ys), bool(act), res)
-    return _InstNormSumFn.apply(res, bool(act), *ys)
+    """(res) + sum_k act(InstanceNorm(y_k)), 1..3 inputs (the kernels take three; a fourth raises)."""
+    return _ops().instance_norm_sum(list(ys), bool(act), res)
 
 
 # ------------------------------------------------------------------------------------------------
 # channels-first LayerNorm
 # ------------------------------------------------------------------------------------------------
-class _LayerNormCFFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta):
-        m = _cpp() if x.is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            out, ctx.cst = m.ln_fwd(x, gamma, beta, H.stream_ptr())
-            return out
-        _check(x, "layer_norm")
-        x = _c(x)
-        B, C = x.shape[:2]
-        V = x[0, 0].numel()
-        out = torch.empty_like(x)
-        H.call("vx_ln_cf_fwd", H.P(x), H.P(gamma), H.P(beta), H.P(out), B, C, V, LN_EPS, H.stream_ptr())
-        ctx.save_for_backward(x)
-        ctx.g, ctx.bt = gamma, beta
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.cst is not None:
-            dx = _cpp_mod().ln_bwd(ctx.cst, dout, H.stream_ptr())
-            ctx.cst = None
-            return dx, None, None
-        (x,) = ctx.saved_tensors
-        dout = _c(dout)
-        B, C = x.shape[:2]
-        V = x[0, 0].numel()
-        dx = torch.empty_like(x)
-        ws = torch.empty((2 * B * V,), device=x.device, dtype=torch.float32)
-        H.call("vx_ln_cf_bwd", H.P(x), H.P(ctx.g), H.P(dout), H.P(dx), H.P(grad_buf(ctx.g)), H.P(grad_buf(ctx.bt)), H.P(ws), B, C, V, LN_EPS, H.stream_ptr())
-        return dx, None, None
-
-
 def layernorm_cf(x, gamma, beta):
-    m = _cpp() if x.is_cuda else None
-    if m is not None:
-        return torch.ops.veloxseg.layer_norm_cf(x, gamma, beta)
-    return _LayerNormCFFn.apply(x, gamma, beta)
+    return _ops().layer_norm_cf(x, gamma, beta)
 
 
 # ------------------------------------------------------------------------------------------------
 # element-wise
 # ------------------------------------------------------------------------------------------------
-class _GeluDropFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, p, site):
-        m = _cpp() if a.is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            h, ctx.cst = m.gelu_fwd(a, float(p), int(site), _rs_ptr(a.device, p), H.stream_ptr())
-            return h
-        _check(a, "gelu")
-        a = _c(a)
-        h = torch.empty_like(a)
-        rs = rng_state(a.device) if p > 0 else None
-        H.call("vx_gelu_drop_fwd", H.P(a), H.P(h), a.numel(), H.P(rs, torch.int64), site, float(p), H.stream_ptr())
-        ctx.save_for_backward(a)
-        ctx.p, ctx.site, ctx.rs = float(p), site, rs
-        return h
-
-    @staticmethod
-    def backward(ctx, dh):
-        if ctx.cst is not None:
-            da = _cpp_mod().gelu_bwd(ctx.cst, dh, H.stream_ptr())
-            ctx.cst = None
-            return da, None, None
-        (a,) = ctx.saved_tensors
-        dh = _c(dh)
-        da = torch.empty_like(a)
-        rs = ctx.rs
-        H.call("vx_gelu_drop_bwd", H.P(dh), H.P(a), H.P(da), a.numel(), H.P(rs, torch.int64), ctx.site, ctx.p, H.stream_ptr())
-        return da, None, None
-
-
 def gelu_dropout(a, p: float = 0.0, site: int = 0):
-    m = _cpp() if a.is_cuda else None
-    if m is not None:
-        return m.gelu(a, float(p), int(site), _rs_ptr(a.device, p))
-    return _GeluDropFn.apply(a, float(p), int(site))
-
-
-class _AxpyDropFn(torch.autograd.Function):
-    """out = alpha * x + dropout(z)  (x may be None)."""
-
-    @staticmethod
-    def forward(ctx, x, z, alpha, p, site):
-        m = _cpp() if z.is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            out, ctx.cst = m.axpy_fwd(x, z, float(alpha), float(p), int(site), _rs_ptr(z.device, p), H.stream_ptr())
-            return out
-        _check(z, "residual_dropout")
-        z = _c(z)
-        xc = _c(x) if x is not None else None
-        out = torch.empty_like(z)
-        rs = rng_state(z.device) if p > 0 else None
-        H.call("vx_axpy_drop_fwd", H.P(xc), H.P(z), H.P(out), float(alpha), z.numel(), H.P(rs, torch.int64), site, float(p), H.stream_ptr())
-        ctx.alpha, ctx.p, ctx.site, ctx.has_x, ctx.rs = float(alpha), float(p), site, x is not None, rs
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.cst is not None:
-            dx, dz = _cpp_mod().axpy_bwd(ctx.cst, dout, bool(ctx.needs_input_grad[0]), H.stream_ptr())
-            ctx.cst = None
-            return dx, dz, None, None, None
-        dout = _c(dout)
-        need_x = ctx.has_x and ctx.needs_input_grad[0]
-        dx = dz = None
-        if ctx.p == 0.0 and (ctx.alpha == 1.0 or not need_x):
-            return (dout if need_x else None), dout, None, None, None
-        if need_x:
-            dx = dout if ctx.alpha == 1.0 else torch.empty_like(dout)
-        dz = dout if ctx.p == 0.0 else torch.empty_like(dout)
-        rs = ctx.rs
-        H.call("vx_axpy_drop_bwd", H.P(dout), H.P(dx) if (need_x and ctx.alpha != 1.0) else None,
-               H.P(dz) if ctx.p > 0 else None, ctx.alpha, dout.numel(), H.P(rs, torch.int64), ctx.site, ctx.p, H.stream_ptr())
-        return dx, dz, None, None, None
+    return cpp_module().gelu(a, float(p), int(site), rs_ptr(a.device, p))
 
 
 def residual_dropout(x, z, alpha: float = 1.0, p: float = 0.0, site: int = 0):
-    m = _cpp() if z.is_cuda else None
-    if m is not None:
-        return m.axpy(x, z, float(alpha), float(p), int(site), _rs_ptr(z.device, p))
-    return _AxpyDropFn.apply(x, z, float(alpha), float(p), int(site))
+    """out = alpha * x + dropout(z)  (x may be None)."""
+    return cpp_module().axpy(x, z, float(alpha), float(p), int(site), rs_ptr(z.device, p))
 
 
 class _AddFn(torch.autograd.Function):
@@ -735,113 +373,28 @@ def add(a, b):
 # ------------------------------------------------------------------------------------------------
 # composite blocks: ONE autograd node for a whole JLC block / transformer FFN tail
 # ------------------------------------------------------------------------------------------------
-# The fine-grained operators above cost ~45 us of host time each per step (autograd node + python + allocations), and the step is
-# host-bound once the GPU side overlaps on several streams.  A composite runs the SAME forward / backward code of
-# those operators (their staticmethods, on a light context object instead of an autograd ctx) in a fixed order, so the kernels, the
-# arithmetic and the dropout streams are identical; only the 8 (JLC) / 4 (FFN) inner autograd nodes and their bookkeeping disappear.
+# The fine-grained operators above cost ~45 us of host time each per step (autograd node + allocations), and the step is host-bound once
+# the GPU side overlaps on several streams.  A composite is ONE C++ autograd node (csrc/_vxops.cpp JLCFn / FFNFn) that runs the
+# block on its fused kernels where they apply and otherwise the forward / backward bodies of those operators in a fixed order; the dropout
+# streams are identical either way.
 USE_COMPOSITE = True
-
-
-class _Ctx:
-    """stand-in for the autograd ctx when an operator's forward/backward staticmethods are called directly"""
-    __slots__ = ("saved_tensors", "needs_input_grad", "__dict__")
-
-    def __init__(self):
-        self.saved_tensors = ()
-        self.needs_input_grad = ()
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
-
-
-def _sum3(a, b, c=None):
-    out = torch.empty_like(a)
-    H.call("vx_add", H.P(a), H.P(_c(b)), H.P(_c(c)) if c is not None else None, H.P(out), a.numel(), H.stream_ptr())
-    return out
-
-
-class _JLCFn(torch.autograd.Function):
-    """x + sum_k GELU(IN(gconv_k(x))) =: o ;  out = o + Drop(conv2(GELU(conv1(IN(o)))))   (reference conv_blocks.py:41-75)"""
-
-    @staticmethod
-    def forward(ctx, x, mod, p, site):
-        m = _cpp() if x.is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            convs = [seq[0] for seq in mod.spatial_convs]
-            l1, l2 = mod.channel_conv[1], mod.channel_conv[3]
-            out, ctx.cst = m.jlc_fwd(x, [c.weight for c in convs], [c.bias for c in convs], convs[0].groups, l1.weight, l1.bias, l2.weight, l2.bias,
-                                     float(p), int(site), _rs_ptr(x.device, p), H.stream_ptr())
-            return out
-        cs, ys = [], []
-        for seq in mod.spatial_convs:
-            conv = seq[0]
-            c = _Ctx()
-            K = conv.kernel_size[0]
-            ys.append(_Conv3dFn.forward(c, x, None, conv.weight, conv.bias, K, 1, K // 2, conv.groups, 1))
-            cs.append(c)
-        c_in1, c_in2, c1, cg, c2, cr = _Ctx(), _Ctx(), _Ctx(), _Ctx(), _Ctx(), _Ctx()
-        o = _InstNormSumFn.forward(c_in1, x, True, *ys)
-        n = _InstNormSumFn.forward(c_in2, None, False, o)
-        l1, l2 = mod.channel_conv[1], mod.channel_conv[3]
-        a = _Conv3dFn.forward(c1, n, None, l1.weight, l1.bias, 1, 1, 0, 1, 1)
-        h = _GeluDropFn.forward(cg, a, 0.0, 0)
-        z = _Conv3dFn.forward(c2, h, None, l2.weight, l2.bias, 1, 1, 0, 1, 1)
-        out = _AxpyDropFn.forward(cr, o, z, 1.0, float(p), int(site))
-        ctx.tape = (cs, c_in1, c_in2, c1, cg, c2, cr)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.cst is not None:
-            dx = _cpp_mod().jlc_bwd(ctx.cst, dout, bool(ctx.needs_input_grad[0]), H.stream_ptr())
-            ctx.cst = None
-            return dx, None, None, None
-        cs, c_in1, c_in2, c1, cg, c2, cr = ctx.tape
-        ctx.tape = None
-        cr.needs_input_grad = (True, True, False, False, False)
-        do_res, dz = _AxpyDropFn.backward(cr, dout)[:2]
-        c2.needs_input_grad = (True,) + (False,) * 8
-        dh = _Conv3dFn.backward(c2, dz)[0]
-        cg.needs_input_grad = (True, False, False)
-        da = _GeluDropFn.backward(cg, dh)[0]
-        c1.needs_input_grad = (True,) + (False,) * 8
-        dn = _Conv3dFn.backward(c1, da)[0]
-        c_in2.needs_input_grad = (False, False, True)
-        do2 = _InstNormSumFn.backward(c_in2, dn)[2]
-        do = _sum3(_c(do_res), do2)
-        n = len(cs)
-        c_in1.needs_input_grad = (True, False) + (True,) * n
-        g = _InstNormSumFn.backward(c_in1, do)
-        dxs = []
-        for k, c in enumerate(cs):
-            c.needs_input_grad = (True,) + (False,) * 8
-            dxs.append(_Conv3dFn.backward(c, g[2 + k])[0])
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        dx = _sum3(do, dxs[0], dxs[1] if n > 1 else None)
-        if n > 2:
-            dx = _sum3(dx, dxs[2])
-        return dx, None, None, None
 
 
 def weights_epoch_bump():
     """the parameters changed through raw pointers (TrainEngine's fused AdamW): weight images kept for inference (jlc_prefetch(keep=True)) are stale from here on"""
-    m = _cpp()
-    return int(m.weights_epoch_bump()) if m is not None and hasattr(m, "weights_epoch_bump") else 0
+    return int(cpp_module().weights_epoch_bump())
 
 
 def weights_epoch() -> int:
-    m = _cpp()
-    return int(m.weights_epoch()) if m is not None and hasattr(m, "weights_epoch") else 0
+    return int(cpp_module().weights_epoch())
 
 
 def jlc_prefetch(mod, grid, stream, keep: bool = False) -> bool:
     """Build the weight images of JLC block `mod` (its next forward runs on a `grid` = (D, H, W) volume) on `stream`, ahead of the block: the block's forward then launches
     no preparation kernels (csrc/_vxops.cpp jlc_prep_into / jlc_fwd_f).  The image buffer is the block's own and is re-used every step; an event recorded on `stream` is left
-    on the block and waited for by its forward.  Returns False where the block builds nothing ahead (VALU convolutions, python bindings)."""
-    m = _cpp()
-    if m is None or len(mod.spatial_convs) != 3 or not hasattr(m, "jlc_prep_into"):
+    on the block and waited for by its forward.  Returns False where the block builds nothing ahead (VALU convolutions)."""
+    m = cpp_module()
+    if len(mod.spatial_convs) != 3:
         return False
     convs = [seq[0] for seq in mod.spatial_convs]
     w = convs[0].weight
@@ -868,9 +421,9 @@ def expand_prefetch(conv, stream, keep: bool = False) -> bool:
     """Both weight images of a patch-expand layer (`conv`: the 3^3 convolution in front of PixelShuffle(4)) built on `stream` ahead of its forward (fp16-piece mode;
     csrc/_vxops.cpp expand_prep_into): the layer's forward and input gradient then launch their matrix kernels only.  The buffers are the layer's own, re-used every step.
     The caller joins `stream` before the layer runs (the engine's encoder-forward stage does)."""
-    m = _cpp()
+    m = cpp_module()
     w = conv.weight
-    if m is None or not hasattr(m, "expand_prep_into") or not w.is_cuda or w.dim() != 5:
+    if not w.is_cuda or w.dim() != 5:
         return False
     n = int(m.expand_img_floats(int(w.shape[0])))
     if n <= 0 or tuple(w.shape[1:]) != (16, 3, 3, 3):
@@ -883,66 +436,23 @@ def expand_prefetch(conv, stream, keep: bool = False) -> bool:
 
 
 def jlc_block(x, mod, p: float, site: int):
-    m = _cpp() if x.is_cuda else None
+    """x + sum_k GELU(IN(gconv_k(x))) =: o ;  out = o + Drop(conv2(GELU(conv1(IN(o)))))   (reference conv_blocks.py:41-75) as one autograd node"""
+    convs = [seq[0] for seq in mod.spatial_convs]
+    if len(convs) > 3:
+        raise RuntimeError(f"veloxseg_amd.jlc_block: {len(convs)} spatial convolutions; the node and its kernels take at most 3")
     ev = mod.__dict__.pop("_pf_ev", None)                      # images prepared ahead on a side stream (jlc_prefetch): this stream waits for them
     if ev is not None:
         torch.cuda.current_stream(x.device).wait_event(ev)
-    if m is not None and len(mod.spatial_convs) <= 3:          # the whole block as one C++ autograd node
-        convs = [seq[0] for seq in mod.spatial_convs]
-        l1, l2 = mod.channel_conv[1], mod.channel_conv[3]
-        w = [c.weight for c in convs] + [None] * (3 - len(convs))
-        b = [c.bias for c in convs] + [None] * (3 - len(convs))
-        return m.jlc(x, w[0], w[1], w[2], b[0], b[1], b[2], convs[0].groups, l1.weight, l1.bias, l2.weight, l2.bias, float(p), int(site), _rs_ptr(x.device, p))
-    return _JLCFn.apply(x, mod, float(p), int(site))
-
-
-class _FFNTailFn(torch.autograd.Function):
-    """out = y + Drop(linear2(Drop(GELU(linear1(LN(y))))))   (reference PWA.py:437 with attention_utils.py:45-71)"""
-
-    @staticmethod
-    def forward(ctx, y, norm, ffn, p):
-        m = _cpp() if y.is_cuda else None
-        ctx.cst = None
-        if m is not None:
-            out, ctx.cst = m.ffn_fwd(y, norm.weight, norm.bias, ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight, ffn.linear2.bias, float(p),
-                                     int(ffn.site1), int(ffn.site2), _rs_ptr(y.device, p), H.stream_ptr())
-            return out
-        cl, c1, cg, c2, cr = _Ctx(), _Ctx(), _Ctx(), _Ctx(), _Ctx()
-        n = _LayerNormCFFn.forward(cl, y, norm.weight, norm.bias)
-        a = _Conv3dFn.forward(c1, n, None, ffn.linear1.weight, ffn.linear1.bias, 1, 1, 0, 1, 1)
-        h = _GeluDropFn.forward(cg, a, float(p), int(ffn.site1))
-        z = _Conv3dFn.forward(c2, h, None, ffn.linear2.weight, ffn.linear2.bias, 1, 1, 0, 1, 1)
-        out = _AxpyDropFn.forward(cr, y, z, 1.0, float(p), int(ffn.site2))
-        ctx.tape = (cl, c1, cg, c2, cr)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.cst is not None:
-            dy = _cpp_mod().ffn_bwd(ctx.cst, dout, H.stream_ptr())
-            ctx.cst = None
-            return dy, None, None, None
-        cl, c1, cg, c2, cr = ctx.tape
-        ctx.tape = None
-        cr.needs_input_grad = (True, True, False, False, False)
-        dy_res, dz = _AxpyDropFn.backward(cr, dout)[:2]
-        c2.needs_input_grad = (True,) + (False,) * 8
-        dh = _Conv3dFn.backward(c2, dz)[0]
-        cg.needs_input_grad = (True, False, False)
-        da = _GeluDropFn.backward(cg, dh)[0]
-        c1.needs_input_grad = (True,) + (False,) * 8
-        dn = _Conv3dFn.backward(c1, da)[0]
-        cl.needs_input_grad = (True, False, False)
-        dy_ln = _LayerNormCFFn.backward(cl, dn)[0]
-        return _sum3(_c(dy_res), dy_ln), None, None, None
+    l1, l2 = mod.channel_conv[1], mod.channel_conv[3]
+    w = [c.weight for c in convs] + [None] * (3 - len(convs))
+    b = [c.bias for c in convs] + [None] * (3 - len(convs))
+    return cpp_module().jlc(x, w[0], w[1], w[2], b[0], b[1], b[2], convs[0].groups, l1.weight, l1.bias, l2.weight, l2.bias, float(p), int(site), rs_ptr(x.device, p))
 
 
 def ffn_tail(y, norm, ffn, p: float):
-    m = _cpp() if y.is_cuda else None
-    if m is not None:                                          # the whole tail as one C++ autograd node
-        return m.ffn(y, norm.weight, norm.bias, ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight, ffn.linear2.bias, float(p), int(ffn.site1), int(ffn.site2),
-                     _rs_ptr(y.device, p))
-    return _FFNTailFn.apply(y, norm, ffn, float(p))
+    """out = y + Drop(linear2(Drop(GELU(linear1(LN(y))))))   (reference PWA.py:437 with attention_utils.py:45-71) as one autograd node"""
+    return cpp_module().ffn(y, norm.weight, norm.bias, ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight, ffn.linear2.bias, float(p), int(ffn.site1), int(ffn.site2),
+                            rs_ptr(y.device, p))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -963,12 +473,7 @@ def _ptrs(vals):
 def _submit_wgrad(fn):
     """run fn(stream_ptr) now on the current stream, or -- while the engine defers weight gradients (csrc/_vxops.cpp WgradQueue) -- queue it with the
     other weight-gradient launches of the pass; fn owns its operands"""
-    m = _cpp_mod()
-    st = H.stream_ptr()
-    if m is not None and hasattr(m, "wgrad_submit_py"):
-        m.wgrad_submit_py(int(st or 0), int(torch.cuda.current_device()), fn)
-    else:
-        fn(st)
+    cpp_module().wgrad_submit_py(int(H.stream_ptr() or 0), int(torch.cuda.current_device()), fn)
 
 
 WGG_JOBS, WGG_FOLDS = 24, 16          # capacity of one vx_pw_wgrad_group launch (csrc/pointwise.hip)
@@ -995,8 +500,7 @@ def _submit_wgrad_jobs(jobs, folds):
     (13 launches at the end of the encoder backward -> 2)."""
     if not jobs and not folds:
         return
-    m = _cpp_mod()
-    if m is None or not hasattr(m, "wgrad_deferring") or not m.wgrad_deferring():
+    if not cpp_module().wgrad_deferring():
         _wgrad_group(jobs, folds, H.stream_ptr())
         return
     key = (int(torch.cuda.current_device()), int(H.stream_ptr() or 0))
@@ -1250,180 +754,30 @@ def pwa_post(ss, xs, mixes, norms, ffns, alpha, p_mix, p_ffn, sites_mix):
     return list(_PwaPostFn.apply(M, float(alpha), float(p_mix), float(p_ffn), tuple(sites), *args))
 
 
-class _SpaceToDepth2Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        _check(x, "space_to_depth")
-        x = _c(x)
-        B, C, D, Hh, W = x.shape
-        assert D % 2 == 0 and Hh % 2 == 0 and W % 2 == 0
-        out = torch.empty((B, 8 * C, D // 2, Hh // 2, W // 2), device=x.device, dtype=torch.float32)
-        H.call("vx_space_to_depth2", H.P(x), H.P(out), B, C, D // 2, Hh // 2, W // 2, 0, H.stream_ptr())
-        ctx.shape = (B, C, D, Hh, W)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        B, C, D, Hh, W = ctx.shape
-        g = _c(g)
-        dx = torch.empty((B, C, D, Hh, W), device=g.device, dtype=torch.float32)
-        H.call("vx_space_to_depth2", H.P(g), H.P(dx), B, C, D // 2, Hh // 2, W // 2, 1, H.stream_ptr())
-        return dx
-
-
 def space_to_depth2(x):
-    m = _cpp() if x.is_cuda else None
-    if m is not None:
-        return torch.ops.veloxseg.space_to_depth2(x)
-    return _SpaceToDepth2Fn.apply(x)
+    return _ops().space_to_depth2(x)
 
 
 # ------------------------------------------------------------------------------------------------
 # Paired-Window Attention core: gather -> attention -> scatter for all modalities
 # ------------------------------------------------------------------------------------------------
-class _PwaCoreFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, table, plan, cq, cv, M, p_attn, site, *qkv):
-        assert len(qkv) == 3 * M
-        qkv = [_c(t) for t in qkv]
-        _check(qkv[0], "pwa_attention")
-        B = qkv[0].shape[0]
-        dev = qkv[0].device
-        h, Nt, ML = plan.heads, plan.Ntot, M * plan.l
-        st = H.stream_ptr()
-        pp = H.ctypes.addressof(plan)
-        tq = torch.empty((B, h, Nt, ML, cq), device=dev, dtype=torch.float32)
-        tk = torch.empty_like(tq)
-        tv = torch.empty((B, h, Nt, ML, cv), device=dev, dtype=torch.float32)
-        iq = torch.empty(tq.shape, device=dev, dtype=torch.int32)
-        ik = torch.empty(tq.shape, device=dev, dtype=torch.int32)
-        iv = torch.empty(tv.shape, device=dev, dtype=torch.int32)
-        srcs_arr = (H.ctypes.c_void_p * (3 * M))(*[H.P(t) for t in qkv])
-        srcs = H.ctypes.addressof(srcs_arr)
-        H.call("vx_pwa_gather_all_fwd", srcs, H.P(tq), H.P(tk), H.P(tv), H.P(iq, torch.int32), H.P(ik, torch.int32), H.P(iv, torch.int32),
-               pp, cq, cv, M, B, st)
-        O = torch.empty_like(tv)
-        lse = torch.empty((B, h, Nt, ML), device=dev, dtype=torch.float32)
-        rs = rng_state(dev) if p_attn > 0 else None
-        tbl = _c(table)
-        mbits = None
-        if p_attn > 0 and H.query("vx_pwa_attn_mbits_useful", pp, B, M, cq, cv) == 1:      # keep bits of the dropout mask for the one-pass backward
-            mbits = torch.empty((H.query("vx_pwa_attn_mbits_words", pp, B, M),), device=dev, dtype=torch.int16)
-        H.call("vx_pwa_attn_fwd_mb", H.P(tq), H.P(tk), H.P(tv), H.P(tbl), H.P(O), H.P(lse), pp, B, M, cq, cv,
-               H.P(rs, torch.int64), site, float(p_attn), H.P(mbits, torch.int16), st)
-        ctx.mbits = mbits
-        g = (plan.grid[0], plan.grid[1], plan.grid[2])
-        outs = []
-        for m in range(M):
-            o = torch.empty((B, plan.nb * h * cv, *g), device=dev, dtype=torch.float32)
-            H.call("vx_pwa_scatter_fwd", H.P(O), H.P(o), pp, cv, m, M, B, st)
-            outs.append(o)
-        ctx.save_for_backward(tq, tk, tv, O, lse, tbl, iq, ik, iv)
-        ctx.qkv_shapes = [tuple(t.shape) for t in qkv]
-        ctx.table = table
-        ctx.plan, ctx.cq, ctx.cv, ctx.M, ctx.p, ctx.site, ctx.rs = plan, cq, cv, M, float(p_attn), site, rs
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *douts):
-        tq, tk, tv, O, lse, tbl, iq, ik, iv = ctx.saved_tensors
-        plan, cq, cv, M = ctx.plan, ctx.cq, ctx.cv, ctx.M
-        B = tq.shape[0]
-        dev = tq.device
-        st = H.stream_ptr()
-        pp = H.ctypes.addressof(plan)
-        dO = torch.zeros_like(O)
-        for m in range(M):
-            H.call("vx_pwa_scatter_bwd", H.P(_c(douts[m])), H.P(dO), pp, cv, m, M, B, st)
-        dq, dk, dv = torch.empty_like(tq), torch.empty_like(tk), torch.empty_like(tv)
-        cache = plan.__dict__.setdefault("_ws_floats", {})          # python-side attribute of the ctypes plan object
-        nws = cache.get((B, M))
-        if nws is None:
-            nws = cache[(B, M)] = H.query("vx_pwa_attn_bwd_ws_floats", pp, B, M)
-        delta = torch.empty(nws, device=dev, dtype=torch.float32)
-        rs = ctx.rs              # the {seed, step} tensor of THIS node's forward
-        dtab = grad_buf(ctx.table) if ctx.table.requires_grad else torch.zeros_like(tbl)
-        H.call("vx_pwa_attn_bwd_mb", H.P(tq), H.P(tk), H.P(tv), H.P(tbl), H.P(O), H.P(lse), H.P(dO), H.P(dq), H.P(dk), H.P(dv),
-               H.P(dtab), H.P(delta), pp, B, M, cq, cv, H.P(rs, torch.int64), ctx.site, ctx.p, H.P(ctx.mbits, torch.int16), st)
-        grads = [torch.empty(shp, device=dev, dtype=torch.float32) for shp in ctx.qkv_shapes]
-        dsts_arr = (H.ctypes.c_void_p * (3 * M))(*[H.P(t) for t in grads])
-        dsts = H.ctypes.addressof(dsts_arr)
-        H.call("vx_pwa_gather_all_bwd", H.P(dq), H.P(dk), H.P(dv), H.P(iq, torch.int32), H.P(ik, torch.int32), H.P(iv, torch.int32), dsts,
-               pp, cq, cv, M, B, st)
-        return (None, None, None, None, None, None, None, *grads)
-
-
 def pwa_core(table, plan, cq, cv, qkv: Sequence[torch.Tensor], p_attn: float = 0.0, site: int = 0) -> List[torch.Tensor]:
-    M = len(qkv) // 3
-    m = _cpp() if qkv[0].is_cuda else None
-    if m is not None and M <= 4:             # the whole core as one C++ autograd node (same C-ABI calls as the python node below)
-        return list(m.pwa_core(table, H.ctypes.addressof(plan), int(cq), int(cv), float(p_attn), int(site), _rs_ptr(qkv[0].device, p_attn), list(qkv)))
-    return list(_PwaCoreFn.apply(table, plan, int(cq), int(cv), M, float(p_attn), int(site), *qkv))
+    """gather -> attention -> scatter for all M = len(qkv) / 3 modalities as one autograd node; M <= 4 (more raises)"""
+    return list(cpp_module().pwa_core(table, H.ctypes.addressof(plan), int(cq), int(cv), float(p_attn), int(site), rs_ptr(qkv[0].device, p_attn), list(qkv)))
 
 
 # ------------------------------------------------------------------------------------------------
 # up-sampling, Gram
 # ------------------------------------------------------------------------------------------------
-class _UpsampleFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, size):
-        _check(x, "upsample_trilinear")
-        x = _c(x)
-        B, C, d, h, w = x.shape
-        D, Hh, W = size
-        out = torch.empty((B, C, D, Hh, W), device=x.device, dtype=torch.float32)
-        H.call("vx_upsample_trilinear_fwd", H.P(x), H.P(out), B * C, d, h, w, D, Hh, W, H.stream_ptr())
-        ctx.shape = (B, C, d, h, w, D, Hh, W)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        B, C, d, h, w, D, Hh, W = ctx.shape
-        g = _c(g)
-        dx = torch.empty((B, C, d, h, w), device=g.device, dtype=torch.float32)
-        ws = torch.empty((B * C * d * (Hh * W + h * W),), device=g.device, dtype=torch.float32)
-        H.call("vx_upsample_trilinear_bwd", H.P(g), H.P(dx), H.P(ws), B * C, d, h, w, D, Hh, W, H.stream_ptr())
-        return dx, None
-
-
 def upsample_trilinear(x, size):
     size = tuple(int(s) for s in size)
     if tuple(x.shape[2:]) == size:
         return x        # F.interpolate to the same size with align_corners=True is the identity (VeloxSeg.py:183)
-    m = _cpp() if x.is_cuda else None
-    if m is not None:
-        return torch.ops.veloxseg.upsample_trilinear(x, list(size))
-    return _UpsampleFn.apply(x, size)
-
-
-class _GramFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        _check(x, "gram")
-        x = _c(x)
-        B, C = x.shape[:2]
-        V = x[0, 0].numel()
-        G = torch.empty((B, C, C), device=x.device, dtype=torch.float32)
-        H.call("vx_gram_fwd", H.P(x), H.P(G), B, C, V, H.stream_ptr())
-        ctx.save_for_backward(x)
-        return G
-
-    @staticmethod
-    def backward(ctx, dG):
-        (x,) = ctx.saved_tensors
-        dG = _c(dG)
-        B, C = x.shape[:2]
-        V = x[0, 0].numel()
-        dx = torch.empty_like(x)
-        H.call("vx_gram_bwd", H.P(x), H.P(dG), H.P(dx), B, C, V, H.stream_ptr())
-        return dx
+    return _ops().upsample_trilinear(x, list(size))
 
 
 def gram(x):
-    m = _cpp() if x.is_cuda else None
-    if m is not None:
-        return torch.ops.veloxseg.gram(x)
-    return _GramFn.apply(x)
+    return _ops().gram(x)
 
 
 # ------------------------------------------------------------------------------------------------
