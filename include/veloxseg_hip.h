@@ -65,7 +65,8 @@ int vx_conv_wgrad_gather_ok(int B, int Cin, int Di, int Hi, int Wi, int Cout, in
 int vx_conv_wgrad_gather_mfma(const float* x, const float* dy, float* dw, float* db, int B, int Cin, int Di, int Hi, int Wi, int Cout, int K, int S, int P, void* stream);
 int vx_conv_wgrad_gather_set(int on);   /* A/B (tests) */
 /* The three weight gradients of a JLC block (grouped convolutions k = 5 / 3 / 1, conv_blocks.py:51-58) at small volumes (<= 512 voxels per sample: the 8^3 / 4^3 levels of
- * the 128^3 configurations, 6^3 / 3^3 of the 96^3 ones) as gather-GEMMs on v_mfma_f32_16x16x4_f32 in ONE launch; dw += ; exact fp32 products. */
+ * the 128^3 configurations, 6^3 / 3^3 of the 96^3 ones) as gather-GEMMs on v_mfma_f32_16x16x4_f32 in ONE launch; dw += ; exact fp32 products.  The three gradients are
+ * formed together: g1, g3, g5 and dw1, dw3, dw5 must all be given (a NULL one is error -1). */
 int vx_jlc_wgrad_gather_ok(int C, int G, int D, int H, int W);
 int vx_jlc_wgrad_gather(const float* x, const float* g1, const float* g3, const float* g5, float* dw1, float* dw3, float* dw5, int B, int C, int G, int D, int H, int W, void* stream);
 int vx_jlc_wgrad_gather_set(int on);   /* A/B (tests) */
@@ -449,7 +450,7 @@ int vx_pwa_attn_set_short(int on);       /* 1 (default): single-modality windows
  * --------------------------------------------------------------------------------------------- */
 int vx_seg_loss_fwd(const float* l0, const float* l1, const float* l2, const float* l3, int nh, const void* labels, int lab_kind,
                     double* acc, int B, int C, long V, void* stream);
-int vx_sqdiff_sum(const float* a, const float* b, long n, double* acc, void* stream);
+int vx_sqdiff_sum(const float* a, const float* b, long n, double* acc, void* stream);   /* acc[0] = sum (a - b)^2: this entry ZEROES acc first (the _bs forms below add into it) */
 /* acc += sum (a - b)^2 with b a channel slice of a wider tensor (b_batch_stride floats between its samples); acc is NOT zeroed: several
  * reconstruction decoders add into one accumulator from their own streams */
 int vx_sqdiff_sum_bs(const float* a, const float* b, long n_per_sample, long b_batch_stride, int B, double* acc, void* stream);

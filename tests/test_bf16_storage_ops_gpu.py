@@ -18,11 +18,9 @@ import torch
 import torch.nn.functional as TF
 
 import bf16_ref as R
+from exact_ref import CANARY, NAN, Guard      # (the canary-fenced output buffer lives with the exact oracles: tests/exact_ref.py)
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-CANARY = 1.5            # (exact in bf16, fp32 and fp64)
 
 
 def _H():
@@ -37,33 +35,6 @@ def _gen(seed):
 
 def _st():
     return torch.cuda.current_stream().cuda_stream
-
-
-class Guard:
-    """an output tensor between two 64-element canaries; `shift` elements of slack in front move its base pointer (shift = 4 bf16 elements: 8-byte aligned, not 16)"""
-
-    def __init__(self, shape, dtype=torch.float32, fill=NAN, shift=0):
-        n = 1
-        for s in shape:
-            n *= int(s)
-        self.lo = 64 + shift
-        self.buf = torch.full((self.lo + n + 64,), CANARY, device="cuda", dtype=dtype)
-        self.t = self.buf[self.lo:self.lo + n].view(*shape)
-        if torch.is_tensor(fill):
-            self.t.copy_(fill.to(device="cuda", dtype=dtype))
-        else:
-            self.t.fill_(fill)
-        if dtype == torch.bfloat16 and shift == 4:
-            assert self.t.data_ptr() % 16 == 8
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def check(self, what):
-        n = self.t.numel()
-        ok = bool((self.buf[:self.lo] == CANARY).all()) and bool((self.buf[self.lo + n:] == CANARY).all())
-        assert ok, f"{what}: the kernel wrote outside its output ({int((self.buf[:self.lo] != CANARY).sum())} elements before, {int((self.buf[self.lo + n:] != CANARY).sum())} after)"
 
 
 def _h16_in(t32, shift=0):

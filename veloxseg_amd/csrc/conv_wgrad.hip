@@ -1136,7 +1136,7 @@ extern "C" int vx_jlc_wgrad_gather_ok(int C, int G, int D, int H, int W) {
     const int CG = C / G;
     return ((CG == 8 || CG == 16 || CG == 4) && (long)D * H * W <= vx_jg_max_v && D > 0 && H > 0 && W > 0) ? 1 : 0;
 }
-/* dw1 / dw3 / dw5 += the weight gradients of the three grouped convolutions of a JLC block (any of the three may be NULL); x, g1, g3, g5: (B, C, D, H, W) */
+/* dw1 / dw3 / dw5 += the weight gradients of the three grouped convolutions of a JLC block (all three are formed in the one launch: none may be NULL); x, g1, g3, g5: (B, C, D, H, W) */
 extern "C" int vx_jlc_wgrad_gather(const float* x, const float* g1, const float* g3, const float* g5, float* dw1, float* dw3, float* dw5, int B, int C, int G, int D, int H, int W,
                                    void* stream) {
     VX_REQUIRE(x && g1 && g3 && g5 && B > 0, "vx_jlc_wgrad_gather: null pointer");
