@@ -595,19 +595,27 @@ def test_upsample_and_gram():
     run_pair(lambda x: VF.gram(x), lambda x: O.gram(x), [x], atol=1e-6, rtol=1e-4, what="gram8")
 
 
-@pytest.mark.parametrize("ncls,M,labdtype", [(2, 2, torch.int64), (4, 1, torch.uint8), (3, 2, torch.int32)])
-def test_loss(ncls, M, labdtype):
+_LOSS_4H = ((1, 1, 1, 1), 0.5, 2.0, 16)          # deep_Loss_weight, RC_Loss_weight, Feature_Loss_weight, side of the Gram matrices
+_LOSS_2H = ((0.6, 0.4), 0.7, 0.3, 8)             # two heads with unequal weights: the configuration the retired Python loss node was compared with the C++ node on
+
+
+@pytest.mark.parametrize("ncls,M,labdtype,terms", [(2, 2, torch.int64, _LOSS_4H), (4, 1, torch.uint8, _LOSS_4H), (3, 2, torch.int32, _LOSS_4H), (2, 2, torch.int64, _LOSS_2H)],
+                         ids=["2-2-labdtype0", "4-1-labdtype1", "3-2-labdtype2", "two_heads_0.6_0.4"])
+def test_loss(ncls, M, labdtype, terms):
     VF = _vf()
     d = dev()
     B, S = 2, 8
+    deep_w, w_rc, w_f, G = terms
+    nh = len(deep_w)
     g = torch.Generator().manual_seed(5)
-    outs = [rnd(B, ncls, S, S, S, seed=i) for i in range(4)] + [rnd(B, M, S, S, S, seed=7)] + [rnd(B, 16, 16, seed=8 + i, scale=0.1) for i in range(1 + M)]
+    outs = [rnd(B, ncls, S, S, S, seed=i) for i in range(nh)] + [rnd(B, M, S, S, S, seed=7)] + [rnd(B, G, G, seed=8 + i, scale=0.1) for i in range(1 + M)]
     lab = torch.randint(0, ncls, (B, 1, S, S, S), generator=g)
     sr = rnd(B, M, S, S, S, seed=99)
-    cfg = {"deep_Loss_weight": [1, 1, 1, 1], "RC_Loss_weight": 0.5, "Feature_Loss_weight": 2.0}
+    cfg = {"deep_Loss_weight": list(deep_w), "RC_Loss_weight": w_rc, "Feature_Loss_weight": w_f}
+    w = tuple(O.normalized_deep_loss_weights(cfg["deep_Loss_weight"], nh))          # (1, 1, 1, 1) -> 0.25 each, as the oracle normalises them
 
     def gfn(*t):
-        return VF.veloxseg_loss(list(t), lab.to(d).to(labdtype), sr.to(d), [0.25] * 4, 0.5, 2.0, M)
+        return VF.veloxseg_loss(list(t), lab.to(d).to(labdtype), sr.to(d), w, w_rc, w_f, M)
 
     def cfn(*t):
         return O.loss(list(t), lab, sr, M, cfg)
@@ -1040,24 +1048,33 @@ def test_pw_conv_bwd_fused_big_equals_two_launches(B, Cin, Cout, V, C1):
 
 
 def test_loss_backward_one_launch_for_all_heads_equals_per_head_launches():
-    VF = _vf()
+    """vx_seg_loss_bwd4 (every head in one launch, what the loss node and StagedLoss call) against vx_seg_loss_bwd (the per-head reference kernel) once per
+    head, through the C ABI on the same coefficients: vx_seg_loss_fwd -> vx_loss_finalize, then both backward forms with go = 1"""
+    from veloxseg_amd import _hip as H
     d = dev()
-    B, S, ncls, M = 2, 12, 3, 2
+    B, S, ncls, nh = 2, 12, 3, 4
+    V = S * S * S
     g = torch.Generator().manual_seed(5)
-    base = [rnd(B, ncls, S, S, S, seed=i) for i in range(4)] + [rnd(B, M, S, S, S, seed=7)] + [rnd(B, 16, 16, seed=8 + i, scale=0.1) for i in range(1 + M)]
+    logits = [rnd(B, ncls, S, S, S, seed=i).to(d) for i in range(nh)]
     lab = torch.randint(0, ncls, (B, 1, S, S, S), generator=g).to(d)
-    sr = rnd(B, M, S, S, S, seed=99).to(d)
-    res = []
-    try:
-        for flag in (True, False):
-            VF.USE_LOSS_BWD4 = flag
-            t = [b.clone().to(d).requires_grad_(True) for b in base]
-            VF.veloxseg_loss(t, lab, sr, [0.4, 0.3, 0.2, 0.1], 0.5, 2.0, M).backward()
-            torch.cuda.synchronize()
-            res.append([x.grad.clone() for x in t])
-    finally:
-        VF.USE_LOSS_BWD4 = True
-    for i, (a, b) in enumerate(zip(*res)):          # the 4-voxel kernel contracts / rounds the soft-max normalisation differently: a few ulp
+    st = H.stream_ptr()
+    lp = [H.P(t) for t in logits]
+    acc = torch.empty(nh * (1 + B * ncls * 3), device=d, dtype=torch.float64)
+    H.call("vx_seg_loss_fwd", *lp, nh, H.P(lab, None), 0, H.P(acc, torch.float64), B, ncls, V, st)
+    hw = torch.tensor([0.4, 0.3, 0.2, 0.1], device=d)
+    stride = 1 + B * ncls * 2
+    coef = torch.empty(nh * stride + 2, device=d)
+    loss = torch.empty(1, device=d)
+    H.call("vx_loss_finalize", H.P(acc, torch.float64), nh, B, ncls, V, H.P(hw), None, 1, 0.0, None, None, None, None, None, 0, 0, 0.0, H.P(loss), H.P(coef), st)
+    go = torch.ones(1, device=d)
+    one = [torch.empty_like(t) for t in logits]
+    H.call("vx_seg_loss_bwd4", *lp, nh, H.P(lab, None), 0, H.P(coef), stride, H.P(go), *[H.P(t) for t in one], B, ncls, V, st)
+    per = [torch.empty_like(t) for t in logits]
+    for h in range(nh):
+        H.call("vx_seg_loss_bwd", lp[h], H.P(lab, None), 0, coef.data_ptr() + 4 * h * stride, H.P(go), H.P(per[h]), B, ncls, V, st)
+    torch.cuda.synchronize()
+    for i, (a, b) in enumerate(zip(one, per)):          # the 4-voxel kernel contracts / rounds the soft-max normalisation differently: a few ulp
+        assert float(b.abs().max()) > 0
         close(a, b, 2e-6 * max(1e-3, float(b.abs().max())), 1e-5, f"grad {i}")
 
 

@@ -621,6 +621,7 @@ template <class S> c10::intrusive_ptr<Holder<S>> put_state(AutogradContext* ctx)
     return h;
 }
 template <class S> S& get_state(AutogradContext* ctx) {
+    TORCH_CHECK(ctx->saved_data.count("st"), "veloxseg_amd: this node's backward already ran; its saved state is released");
     return c10::static_intrusive_pointer_cast<Holder<S>>(ctx->saved_data["st"].toCapsule())->s;
 }
 inline void* cur_stream(const Tensor& t) {          // (a CPU tensor is refused here, before anything touches HIP)
@@ -1309,8 +1310,9 @@ struct FFNFn : public torch::autograd::Function<FFNFn> {
 };
 
 
-// The VeloxSeg loss (utils/loss.py:52-66: sum_h w_h (CE + Dice)(logits_h) + w_rc MSE(rcs, x) + w_f / M sum_m MSE(G_seg, G_m)) as a C++ autograd node: the same C-ABI
-// sequence as functional._VeloxLossFn (deep-supervision heads on coarser grids are interpolated inside the kernels of loss_ds.hip), no interpreter, no Python state.
+// The VeloxSeg loss (utils/loss.py:52-66: sum_h w_h (CE + Dice)(logits_h) + w_rc MSE(rcs, x) + w_f / M sum_m MSE(G_seg, G_m)) as a C++ autograd node, the one
+// host body of the fused loss (functional.veloxseg_loss / seg_only_loss and torch.ops.veloxseg.seg_loss all end here; functional.StagedLoss is the same loss taken apart for the
+// taped step).  Deep-supervision heads on coarser grids are interpolated inside the kernels of loss_ds.hip.  No interpreter, no Python state.
 // outputs = nh logits [+ rcs, G_seg, G_rc x M]
 struct LossState {
     std::vector<Tensor> logits, tail;          // tail: rcs, sr, G_seg, G_m...
@@ -1344,6 +1346,7 @@ struct LossFn : public torch::autograd::Function<LossFn> {
         const int M = (int)num_modal;
         const int nh = (int)outs.size() - (M > 0 ? 2 + M : 0);
         TORCH_CHECK(nh >= 1 && nh <= 4 && (int)head_w.size() == nh, "veloxseg::seg_loss: 1..4 deep-supervision heads with one weight each (got ", nh, " heads, ", head_w.size(), " weights)");
+        TORCH_CHECK(M >= 0 && M <= 4, "veloxseg::seg_loss: 0..4 modalities (the Gram kernels take four teacher matrices), got ", M);
         check_in(outs[0], "seg_loss");
         for (int i = 0; i < nh; ++i) st.logits.push_back(contig(outs[i]));
         const Tensor& l0 = st.logits[0];
@@ -1432,7 +1435,7 @@ struct LossFn : public torch::autograd::Function<LossFn> {
 // =================================================================================================================== python surface
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Dispatcher registration (north_star: "re-registered as custom ops backed by hand-written HIP kernels").  Schemas are defined HERE (veloxseg_amd/ops.py lists them and adds
-// the operators whose bodies need Python-side state: dropout sites, the PWA plan, the loss).  Keys:
+// the two dropout operators whose bodies fetch the Python-side RNG state).  Keys:
 //   Autograd  -> the operator's torch::autograd::Function (forward + backward launch the kernels of include/veloxseg_hip.h)
 //   CUDA      -> the same forward without a graph (inference mode reaches this key directly)
 //   Meta      -> shapes only (FakeTensor / torch.export / torch.compile tracing)

@@ -7,8 +7,8 @@ returned to autograd for them: no per-parameter AccumulateGrad kernels, one flat
 the RCCL all-reduce and the fused AdamW (see veloxseg_amd/engine.py).
 
 The host side of the convolutions, norms, element-wise operators and composite blocks -- kernel selection, workspaces, autograd nodes -- is C++
-(csrc/_vxops.cpp); the functions here call those nodes directly or through torch.ops.veloxseg.*.  The fused PWA chains, the fan-out and the loss
-are Python autograd functions over the same C ABI.
+(csrc/_vxops.cpp); the functions here call those nodes directly or through torch.ops.veloxseg.*, the fused loss among them (torch.ops.veloxseg.seg_loss).
+The fused PWA chains and the fan-out are Python autograd functions over the same C ABI; StagedLoss, the loss taken apart for the taped step, calls it without autograd.
 
 There is no CPU implementation here on purpose (tier rule: the product path has no fallback).
 """
@@ -18,6 +18,7 @@ import itertools
 import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _hip as H
@@ -33,7 +34,6 @@ USE_IN_ROW = True                             # InstanceNorm of short rows (V <=
 IN_ROW_MAX = 4096
 USE_WGRAD_WS = False                          # tiled weight gradient through a partial-sum workspace (deterministic order) instead of float atomics (30 fewer launches per step: +2 %)
 USE_PATCHIFY = True                           # kernel == stride convs (PatchEmbed) as patchify + 1x1 conv (False = generic direct conv)
-USE_LOSS_BWD4 = True                          # loss backward of all deep-supervision heads in one launch (False = one launch per head)
 USE_GCONV1 = True                             # dedicated weight-gradient kernel of the 1x1x1 grouped JLC conv (False = tiled kernel)
 PW_MFMA_MAX_V = 4096                          # 1x1 convs on volumes up to this many voxels use the MFMA tile kernel
 BRANCH_STREAMS = True                         # independent sub-networks (M+1 decoders; encoder conv chain vs PWA chain) run on forked HIP streams
@@ -794,108 +794,17 @@ def _head_weights(ws, device):
     return _weight_cache[key]
 
 
-class _VeloxLossFn(torch.autograd.Function):
-    """sum_h w_h (CE + Dice)(logits_h) + w_rc MSE(rcs, x) + w_f/M sum_m MSE(G_seg, G_m)   (utils/loss.py:52-66)."""
-
-    @staticmethod
-    def forward(ctx, labels, sr, head_w, w_rc, w_f, nh, M, *outs):
-        logits = [_c(t) for t in outs[:nh]]
-        _check(logits[0], "loss")
-        B, C = logits[0].shape[:2]
-        V = logits[0][0, 0].numel()
-        dev = logits[0].device
-        st = H.stream_ptr()
-        if labels.dtype not in _LAB_KIND:
-            raise RuntimeError(f"labels must be int64/int32/uint8, got {labels.dtype}")
-        labels = _c(labels)
-        assert labels.numel() == B * V, (labels.shape, B, V)
-        hw = _head_weights(head_w, dev)
-        seg_acc = torch.empty((nh * (1 + B * C * 3),), device=dev, dtype=torch.float64)
-        lp = [H.P(t) for t in logits] + [None] * (4 - nh)
-        # heads on their own (coarser) grids: the trilinear up-sampling of VeloxSeg.scale_prediction runs INSIDE the loss kernels (csrc/loss_ds.hip)
-        ctx.ds = None
-        if any(tuple(t.shape[2:]) != tuple(logits[0].shape[2:]) for t in logits[1:]):
-            D_, H_, W_ = (int(s_) for s_ in logits[0].shape[2:])
-            if not H.query("vx_seg_loss_ds_ok", C, D_, H_, W_):
-                raise RuntimeError("veloxseg_loss: deep-supervision heads on coarser grids need C in 2..4 and W % 4 == 0 with W/4 dividing 64; up-sample them first")
-            dims = (H.ctypes.c_int * (3 * max(nh - 1, 1)))(*[int(v) for t in logits[1:] for v in t.shape[2:]])
-            ctx.ds = (dims, D_, H_, W_)
-            H.call("vx_seg_loss_ds_fwd", *lp, H.ctypes.addressof(dims), nh, H.P(labels, None), _LAB_KIND[labels.dtype], H.P(seg_acc, torch.float64), B, C, D_, H_, W_, st)
-        else:
-            H.call("vx_seg_loss_fwd", *lp, nh, H.P(labels, None), _LAB_KIND[labels.dtype], H.P(seg_acc, torch.float64), B, C, V, st)
-        has_tail = M > 0
-        rcs = grams = None
-        rc_acc = None
-        if has_tail:
-            rcs, sr_c = _c(outs[nh]), _c(sr)
-            assert rcs.shape == sr_c.shape, (rcs.shape, sr_c.shape)
-            rc_acc = torch.empty((1,), device=dev, dtype=torch.float64)
-            H.call("vx_sqdiff_sum", H.P(rcs), H.P(sr_c), rcs.numel(), H.P(rc_acc, torch.float64), st)
-            grams = [_c(t) for t in outs[nh + 1: nh + 2 + M]]
-        coef = torch.empty((nh * (1 + B * C * 2) + 2,), device=dev, dtype=torch.float32)
-        loss = torch.empty((1,), device=dev, dtype=torch.float32)
-        gp = [H.P(g) for g in grams[1:]] + [None] * (4 - M) if has_tail else [None] * 4
-        H.call("vx_loss_finalize", H.P(seg_acc, torch.float64), nh, B, C, V, H.P(hw),
-               H.P(rc_acc, torch.float64) if has_tail else None, rcs.numel() if has_tail else 1, float(w_rc),
-               H.P(grams[0]) if has_tail else None, *gp, M if has_tail else 0, grams[0].shape[1] if has_tail else 0, float(w_f),
-               H.P(loss), H.P(coef), st)
-        ctx.save_for_backward(labels, coef, *logits, *( [rcs, sr_c] + grams if has_tail else []))
-        ctx.nh, ctx.M, ctx.has_tail, ctx.dims = nh, M, has_tail, (B, C, V)
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        nh, M = ctx.nh, ctx.M
-        B, C, V = ctx.dims
-        labels, coef = ctx.saved_tensors[:2]
-        logits = ctx.saved_tensors[2:2 + nh]
-        st = H.stream_ptr()
-        go = _c(gout.reshape(1).to(torch.float32))
-        grads = []
-        stride = (1 + B * C * 2) * 4
-        if ctx.ds is not None:                    # fused: gradients of the coarse heads through the adjoint of the interpolation, 2 launches
-            dims, D_, H_, W_ = ctx.ds
-            grads = [torch.empty_like(logits[h]) for h in range(nh)]
-            nws = H.query("vx_seg_loss_ds_ws_floats", H.ctypes.addressof(dims), nh, B, C, D_)
-            ws = torch.empty((max(nws, 1),), device=go.device, dtype=torch.float32)
-            H.call("vx_seg_loss_ds_bwd", *([H.P(t) for t in logits] + [None] * (4 - nh)), H.ctypes.addressof(dims), nh, H.P(labels, None), _LAB_KIND[labels.dtype],
-                   coef.data_ptr(), stride // 4, H.P(go), *([H.P(d) for d in grads] + [None] * (4 - nh)), H.P(ws), B, C, D_, H_, W_, st)
-        elif USE_LOSS_BWD4 and nh <= 4:             # every head in one launch: the labels are read once
-            grads = [torch.empty_like(logits[h]) for h in range(nh)]
-            H.call("vx_seg_loss_bwd4", *([H.P(t) for t in logits] + [None] * (4 - nh)), nh, H.P(labels, None), _LAB_KIND[labels.dtype], coef.data_ptr(), stride // 4,
-                   H.P(go), *([H.P(d) for d in grads] + [None] * (4 - nh)), B, C, V, st)
-        else:
-            for h in range(nh):
-                d = torch.empty_like(logits[h])
-                H.call("vx_seg_loss_bwd", H.P(logits[h]), H.P(labels, None), _LAB_KIND[labels.dtype], coef.data_ptr() + h * stride, H.P(go), H.P(d), B, C, V, st)
-                grads.append(d)
-        if ctx.has_tail:
-            rcs, sr = ctx.saved_tensors[2 + nh: 4 + nh]
-            grams = ctx.saved_tensors[4 + nh:]
-            misc = coef.data_ptr() + nh * stride
-            drc = torch.empty_like(rcs)
-            H.call("vx_mse_bwd", H.P(rcs), H.P(sr), misc, H.P(go), H.P(drc), rcs.numel(), st)
-            grads.append(drc)
-            dgs = torch.empty_like(grams[0])
-            dgm = [torch.empty_like(g) for g in grams[1:]]
-            gp = [H.P(g) for g in grams[1:]] + [None] * (4 - M)
-            dp = [H.P(g) for g in dgm] + [None] * (4 - M)
-            H.call("vx_gram_mse_bwd", H.P(grams[0]), *gp, M, misc + 4, H.P(go), H.P(dgs), *dp, grams[0].numel(), st)
-            grads.append(dgs)
-            grads.extend(dgm)
-        return (None, None, None, None, None, None, None, *grads)
-
-
 class StagedLoss:
-    """The VeloxSeg loss (utils/loss.py:52-66) taken apart for the staged training step (engine.TrainEngine): the kernels of _VeloxLossFn, but
-    every decoder branch runs ITS part on its own stream -- the Seg branch the deep-supervision CE + Dice sums and, later, their gradients; each
+    """The VeloxSeg loss (utils/loss.py:52-66) taken apart for the staged training step (engine.TrainEngine): the accumulators, `finalize` and
+    coefficients of the fused loss node (csrc/_vxops.cpp LossFn), but every decoder branch runs ITS part on its own stream -- the Seg branch the deep-supervision CE + Dice sums and, later, their gradients; each
     reconstruction branch its sum of squares against its channels of the input and, later, its MSE gradient -- and only the one-wave `finalize`
     (scalar loss, Dice coefficients, Gram term) sits between the forward and the backward fans.  Same arithmetic, same accumulators, same
-    coefficients as the fused autograd function; nothing here is differentiated by autograd (the gradients are handed to autograd.backward)."""
+    coefficients as the fused node; nothing here is differentiated by autograd (the gradients are handed to autograd.backward)."""
 
     def __init__(self, head_weights, w_rc, w_f, num_modal):
         self.head_weights, self.w_rc, self.w_f, self.M = tuple(float(w) for w in head_weights), float(w_rc), float(w_f), int(num_modal)
         self.nh = len(self.head_weights)
+        self._drc, self.n_rc_expected = {}, None
 
     def begin(self, dev, B, C):
         """fresh accumulators (zero-filled here, i.e. before the forward fan: the branches only add)"""
@@ -904,6 +813,7 @@ class StagedLoss:
         self.rc_acc = torch.zeros((1,), device=dev, dtype=torch.float64)
         self.n_rc = 0
         self.ds = None
+        self._drc, self.n_rc_expected = {}, None          # (a pass hands out only the MSE gradients its own rc_forward formed)
 
     def seg_forward(self, logits, labels):
         logits = [_c(t) for t in logits]
@@ -941,15 +851,13 @@ class StagedLoss:
         """this branch's sum of squares against its channels of the input AND -- the coefficient 2 w_rc / N_rc is known already: the reconstructions cover the input, so
         N_rc = x.numel() (checked in finalize) -- its MSE gradient, in one pass (vx_sqdiff_sum_grad_bs); rc_backward hands the stored gradient out.
         A bfloat16 reconstruction (bf16 storage mode) gets a bfloat16 gradient; the sum of squares is formed in fp32 / fp64 either way."""
-        import numpy as _np
         rc = _c(rc)
         ptr, bstride, n = self._slice(x, ch_off, rc.shape[1])
         assert rc[0].numel() == n and x.is_contiguous()
         self.n_rc_expected = int(x.numel())
-        scale = float(_np.float32(2.0 * self.w_rc / float(self.n_rc_expected))) if self.w_rc != 0.0 else 0.0
+        scale = float(np.float32(2.0 * self.w_rc / float(self.n_rc_expected))) if self.w_rc != 0.0 else 0.0
         drc = torch.empty_like(rc)
         H.call("vx_sqdiff_sum_grad_bs_h", H.P(rc, None), ptr, n, bstride, rc.shape[0], H.P(self.rc_acc, torch.float64), scale, H.P(drc, None), int(rc.dtype == torch.bfloat16), H.stream_ptr())
-        self._drc = getattr(self, "_drc", {})
         self._drc[int(ch_off)] = drc
         return rc
 
@@ -957,7 +865,7 @@ class StagedLoss:
         """-> scalar loss (device tensor); keeps the coefficients and the Gram gradients for the backward fans"""
         dev = self.seg_acc.device
         nh, B, C, M = self.nh, self.B, self.C, self.M
-        if getattr(self, "n_rc_expected", None) is not None and int(n_rc) != self.n_rc_expected:
+        if self.n_rc_expected is not None and int(n_rc) != self.n_rc_expected:
             raise RuntimeError(f"staged loss: the reconstruction branches cover {int(n_rc)} elements, the input has {self.n_rc_expected}: the MSE gradient formed in the forward used the wrong 1 / N")
         st = H.stream_ptr()
         hw = _head_weights(self.head_weights, dev)
@@ -996,7 +904,7 @@ class StagedLoss:
         return grads
 
     def rc_backward(self, rc, x, ch_off):
-        drc = getattr(self, "_drc", {}).get(int(ch_off))
+        drc = self._drc.get(int(ch_off))
         if drc is not None and drc.shape == rc.shape:
             return drc                                   # formed by rc_forward
         ptr, bstride, n = self._slice(x, ch_off, rc.shape[1])
@@ -1009,12 +917,10 @@ class StagedLoss:
 
 def veloxseg_loss(outputs: Sequence[torch.Tensor], labels: torch.Tensor, sr_labels: Optional[torch.Tensor], head_weights: Sequence[float],
                   w_rc: float, w_f: float, num_modal: int) -> torch.Tensor:
-    """outputs = nh logits [+ rcs, G_seg, G_rc x M]."""
-    tail = 2 + num_modal
-    nh = len(outputs) - tail
-    assert 1 <= nh <= 4, "1..4 deep-supervision heads supported"
-    return _VeloxLossFn.apply(labels, sr_labels, tuple(head_weights), float(w_rc), float(w_f), nh, num_modal, *outputs)
+    """sum_h w_h (CE + Dice)(logits_h) + w_rc MSE(rcs, x) + w_f/M sum_m MSE(G_seg, G_m)   (utils/loss.py:52-66) as one autograd node.
+    outputs = nh logits [+ rcs, G_seg, G_rc x M]; 1 <= nh <= 4 with one weight each (the node refuses anything else)."""
+    return _ops().seg_loss(list(outputs), labels, sr_labels, [float(w) for w in head_weights], float(w_rc), float(w_f), int(num_modal))
 
 
 def seg_only_loss(outputs: Sequence[torch.Tensor], labels: torch.Tensor, head_weights: Sequence[float]) -> torch.Tensor:
-    return _VeloxLossFn.apply(labels, None, tuple(head_weights), 0.0, 0.0, len(outputs), 0, *outputs)
+    return veloxseg_loss(outputs, labels, None, head_weights, 0.0, 0.0, 0)

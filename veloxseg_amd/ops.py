@@ -16,7 +16,8 @@ a CPU tensor raises the library's "no CPU path" error -- there is no fallback ke
     torch.ops.veloxseg.seg_loss(outputs, labels, sr_labels, head_weights, w_rc, w_f, num_modal)                          utils/loss.py:52-66
 
 The modules of veloxseg_amd.model reach the seven generic operators THROUGH the dispatcher (functional.py routes conv3d, conv_transpose_k2s2, instance_norm_sum,
-layer_norm_cf, space_to_depth2, upsample_trilinear and gram to torch.ops.veloxseg.*); the composite operators are called as functions of veloxseg_amd.functional.
+layer_norm_cf, space_to_depth2, upsample_trilinear and gram to torch.ops.veloxseg.*), and so does the eager loss (functional.veloxseg_loss / seg_only_loss call
+seg_loss); the other composite operators are called as functions of veloxseg_amd.functional, which hand the same C++ nodes their Python-side state.
 There is one host path per operator: the C++ autograd node behind these schemas."""
 import torch
 

@@ -1,5 +1,5 @@
-"""Deep-supervised CE + Dice, MSE reconstruction and SDKT Gram loss (reference: utils/loss.py:10-86), one fused
-HIP autograd op (veloxseg_amd.functional.veloxseg_loss)."""
+"""Deep-supervised CE + Dice, MSE reconstruction and SDKT Gram loss (reference: utils/loss.py:10-86): one fused HIP autograd op, the C++ node behind
+torch.ops.veloxseg.seg_loss, which veloxseg_amd.functional.veloxseg_loss calls; the taped training step takes the same loss apart (functional.StagedLoss)."""
 import torch
 from torch import nn
 
