@@ -516,22 +516,28 @@ int vx_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr
 int vx_sw_extract(const float* vol, float* win, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0, void* stream);
 /* acc[:, window] += weight * win; windows must be accumulated in the reference's window order (one call each) */
 int vx_sw_accumulate(const float* win, float* acc, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0, float weight, void* stream);
-/* out = acc / (cz[z]*cy[y]*cx[x]) (per-axis window counts; out may alias acc or be NULL), labels = uint8 argmax over C (may be NULL) */
+/* out = acc / ((cz[z]*cy[y])*cx[x]) in IEEE fp32 (per-axis window counts; out may alias acc or be NULL), labels = uint8 arg-max over C of the quotient (may be
+ * NULL; not both).  Arg-max rule, here and in vx_argmax_channels: a column with a NaN gives the index of its first NaN, any other the index of its first maximum
+ * (-0.0 == +0.0).  C <= 256. */
 int vx_sw_finalize(const float* acc, float* out, unsigned char* labels, const float* cz, const float* cy, const float* cx,
                    int C, int D, int H, int W, void* stream);
 /* labels[b, v] = argmax_c logits[b, c, v] (first maximum, uint8): `outputs[0].argmax(dim=1)` of utils/metric/metrics.py:16 */
 int vx_argmax_channels(const float* logits, unsigned char* labels, int B, int C, long V, void* stream);
 /* conf[b, g, p] += #voxels with ground truth g and prediction p (uint64, NC*NC per sample; caller zeroes it): the sufficient statistic of
- * metrics_tensor (utils/metric/metrics.py:44-91) and cal_dice (utils/metric/metrics_brats.py:31-35); label widths 1, 4 or 8 bytes */
+ * metrics_tensor (utils/metric/metrics.py:44-91) and cal_dice (utils/metric/metrics_brats.py:31-35); label widths (pred, gt) in bytes: (1,1), (1,4), (1,8), (4,4),
+ * (8,1), (8,8), any other pair fails with -3; 2 <= NC <= 8.  A label is clamped in its own width before it is counted: < 0 is class 0, >= NC is class NC-1. */
 int vx_confusion(const void* pred, int pred_bytes, const void* gt, int gt_bytes, unsigned long long* conf, int B, long V, int NC, void* stream);
 
 /* ---- training-input stand-in: MONAI CropForegroundd / RandCropByPosNegLabeld / RandRotated of utils/train_autopet.py:132-152 ----
  * x: one sample (C, D, H, W) fp32; labels uint8 / int32 / int64 / fp32 (lab_bytes 1 / 4 / 8 / -4). */
-int vx_min_value(const float* x, long n, float* out_init_inf, void* stream);                       /* out[0] = min(out[0], min x); caller presets +inf */
-int vx_bbox_gt(const float* x, float thr, int C, int D, int H, int W, int* out6, void* stream);     /* (min d,h,w, max d,h,w) of {x > thr}; caller presets (INT_MAX x3, -1 x3) */
+int vx_min_value(const float* x, long n, float* out_init_inf, void* stream);                       /* out[0] = min(out[0], min x); caller presets +inf; NaN voxels are ignored (numpy's x.min() would be NaN) */
+int vx_bbox_gt(const float* x, float thr, int C, int D, int H, int W, int* out6, void* stream);     /* (min d,h,w, max d,h,w) of {x > thr}; caller presets (INT_MAX x3, -1 x3), left as they are when the set is empty; NaN voxels are ignored (NaN > thr is false) */
 int vx_label_chunk_count(const void* labels, int lab_bytes, long n, int chunk, int fg, int* counts, void* stream);   /* per-chunk counts of label > 0 (fg) or == 0 */
+/* out_index[0] = flat index of the k-th (0-based) match in [chunk_start, min(chunk_start + chunk, n)); when the chunk holds k or fewer matches out_index[0] is NOT written
+ * (a preset -1 stays -1).  Both entries: chunk >= 256; a float label is foreground when > 0, background otherwise (0, negatives and NaN). */
 int vx_label_kth_in_chunk(const void* labels, int lab_bytes, long n, long chunk_start, int chunk, int fg, int k, long* out_index, void* stream);
-/* rotation about the last spatial axis (the (D,H) plane turns), centre (n-1)/2, border padding; mode 0 bilinear, 1 nearest */
+/* rotation about the last spatial axis (the (D,H) plane turns), centre (n-1)/2, border padding (the coordinate is clamped, then sampled); mode 0 bilinear, 1 nearest
+ * (round half to even); out must not alias x; cos_a and sin_a are taken as given (they need not form a rotation) */
 int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float cos_a, float sin_a, int mode, void* stream);
 
 /* ---- dense strided convolution on MFMA (groups = 1; k odd <= 7, stride 2..4, pad = k / 2): the DownConv layers between the encoder levels and the

@@ -21,14 +21,16 @@ LIMIT = float(1 << 24)  # integers below 2^24 are exact in fp32
 
 
 class Guard:
-    """an output tensor between two 64-element canaries; `shift` elements of slack in front move its base pointer (shift = 4 bf16 elements: 8-byte aligned, not 16)"""
+    """an output tensor between two 64-element canaries; `shift` elements of slack in front move its base pointer (shift = 4 bf16 elements: 8-byte aligned, not 16);
+    `canary` for integer dtypes, which cannot hold 1.5"""
 
-    def __init__(self, shape, dtype=torch.float32, fill=NAN, shift=0):
+    def __init__(self, shape, dtype=torch.float32, fill=NAN, shift=0, canary=CANARY):
         n = 1
         for s in shape:
             n *= int(s)
         self.lo = 64 + shift
-        self.buf = torch.full((self.lo + n + 64,), CANARY, device="cuda", dtype=dtype)
+        self.canary = canary
+        self.buf = torch.full((self.lo + n + 64,), canary, device="cuda", dtype=dtype)
         self.t = self.buf[self.lo:self.lo + n].view(*shape)
         if torch.is_tensor(fill):
             self.t.copy_(fill.to(device="cuda", dtype=dtype))
@@ -43,8 +45,9 @@ class Guard:
 
     def check(self, what):
         n = self.t.numel()
-        ok = bool((self.buf[:self.lo] == CANARY).all()) and bool((self.buf[self.lo + n:] == CANARY).all())
-        assert ok, f"{what}: the kernel wrote outside its output ({int((self.buf[:self.lo] != CANARY).sum())} elements before, {int((self.buf[self.lo + n:] != CANARY).sum())} after)"
+        c = self.canary
+        ok = bool((self.buf[:self.lo] == c).all()) and bool((self.buf[self.lo + n:] == c).all())
+        assert ok, f"{what}: the kernel wrote outside its output ({int((self.buf[:self.lo] != c).sum())} elements before, {int((self.buf[self.lo + n:] != c).sum())} after)"
 
 
 # ---------------------------------------------------------------------------------------------------------------------- integer generators

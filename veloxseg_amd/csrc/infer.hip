@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(256) vx_argmax_k(const float* __restrict__ log
     }
 }
 
-// conf[b, g, p] = #voxels of sample b with ground truth g and prediction p (classes >= NC are clamped to NC-1); LDS histogram per block
+// conf[b, g, p] = #voxels of sample b with ground truth g and prediction p (labels < 0 count as class 0, labels >= NC as class NC-1); LDS histogram per block
 template <typename TP, typename TG>
 __global__ void __launch_bounds__(256) vx_confusion_k(const TP* __restrict__ pred, const TG* __restrict__ gt, unsigned long long* __restrict__ conf, long V, int NC) {
     __shared__ unsigned int h[64];
@@ -84,9 +84,10 @@ __global__ void __launch_bounds__(256) vx_confusion_k(const TP* __restrict__ pre
     const TP* __restrict__ p = pred + (long)b * V;
     const TG* __restrict__ g = gt + (long)b * V;
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long)gridDim.x * 256) {
-        int pi = (int)p[v], gi = (int)g[v];
-        pi = pi < 0 ? 0 : (pi >= NC ? NC - 1 : pi);
-        gi = gi < 0 ? 0 : (gi >= NC ? NC - 1 : gi);
+        const TP pv = p[v];                       // clamped in the SOURCE width, narrowed after: an int64 label of 2^32 + 1 is class NC-1, not class 1
+        const TG gv = g[v];
+        const int pi = pv < (TP)0 ? 0 : (pv >= (TP)NC ? NC - 1 : (int)pv);
+        const int gi = gv < (TG)0 ? 0 : (gv >= (TG)NC ? NC - 1 : (int)gv);
         atomicAdd(&h[gi * NC + pi], 1u);
     }
     __syncthreads();

@@ -31,7 +31,10 @@ def confusion(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch.T
     for t in (pred, gt):
         if t.dtype not in _BYTES:
             raise TypeError(f"label dtype {t.dtype} not supported (uint8 / int32 / int64)")
-    if _BYTES[pred.dtype] == 4 and _BYTES[gt.dtype] != 4 or _BYTES[pred.dtype] == 8 and _BYTES[gt.dtype] == 4:
+    # the three width pairs the kernel has no instance for are WIDENED to one it has (never narrowed: a label is clamped in its source width)
+    if _BYTES[pred.dtype] == 4 and _BYTES[gt.dtype] == 8:
+        pred = pred.to(torch.int64)
+    elif _BYTES[pred.dtype] == 4 and _BYTES[gt.dtype] == 1 or _BYTES[pred.dtype] == 8 and _BYTES[gt.dtype] == 4:
         gt = gt.to(pred.dtype)
     B = pred.shape[0]
     V = pred[0].numel()

@@ -18,8 +18,10 @@ def _planes(t: torch.Tensor) -> torch.Tensor:
 
 
 def _slice_conf(output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """(B, 1, D, H, W) label maps -> (B*W, 4, 4) confusion matrices"""
-    return confusion(_planes(output), _planes(target), 4)
+    """(B, 1, D, H, W) label maps -> (B*W, 5, 5) confusion matrices: classes 0..3 and a fifth, "other", for every label above 3 -- as in the
+    reference such a voxel is non-zero (WT) but neither ET (== 3) nor TC ({1, 3}); a raw BraTS label 4 is therefore not scored as 3.
+    (A negative label counts as background here; the reference would call it non-zero.  Label maps are never negative.)"""
+    return confusion(_planes(output), _planes(target), 5)
 
 
 def _dice_from(inter, so, st, eps=1e-6):
