@@ -540,6 +540,40 @@ int vx_label_kth_in_chunk(const void* labels, int lab_bytes, long n, long chunk_
  * (round half to even); out must not alias x; cos_a and sin_a are taken as given (they need not form a rotation) */
 int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float cos_a, float sin_a, int mode, void* stream);
 
+/* ---- volume preprocessing (csrc/preprocess.hip): foreground z-score, CT clip + normalise, dataset order statistics, separable resampling -----------------
+ * Reference: preprocess/normalization_MRI.py:7-12,52, preprocess/normalization_CT_PET.py:6-11,23-31,65-81, utils/inference_extern_mri.py:73-75,95.
+ * Volumes are fp32 contiguous, indexed with `long`; masks / labels are uint8 / int32 / int64 / fp32 (bytes code 1 / 4 / 8 / -4, as in vx_label_chunk_count),
+ * a voxel is selected when mask > 0.  fp64 quantities travel through device pointers only.
+ *
+ * Moments.  Selected set = {x > *thr} (thr a device float, NULL = no threshold) intersected with {mask > 0} (mask NULL = no mask); NaN > thr is false.
+ * vx_moments_partials writes, for each of its vx_moments_blocks() blocks b, ws[b] = count, ws[G + b] = sum(x - c), ws[2G + b] = sum((x - c)^2) in fp64 with
+ * c = *center (0 when NULL); ws holds vx_moments_ws_doubles() doubles.  vx_moments_reduce (one block) adds the partials in a fixed order: into acc[3] when
+ * given (accumulate = 1 adds to what acc holds: the union over several volumes), and with phase 0 writes stats[0] = count, stats[1] = sum / count; with phase 1
+ * stats[2] = sqrt(sum of squares / count) (both 0 when count is 0); phase -1 leaves stats alone.  No floating-point atomics: equal inputs give equal bits.
+ * vx_moments_stats = partials, reduce(phase 0), partials(center = stats + 1), reduce(phase 1): the two-pass mean / population std of numpy, stats[3] on the device. */
+int vx_moments_blocks(void);
+int vx_moments_ws_doubles(void);
+int vx_moments_partials(const float* x, long n, const float* thr, const void* mask, int mask_bytes, const double* center, double* ws, void* stream);
+int vx_moments_reduce(const double* ws, double* acc, int accumulate, double* stats, int phase, void* stream);
+int vx_moments_stats(const float* x, long n, const float* thr, double* ws, double* stats, void* stream);
+/* out = (clip(x, lo, hi) - mean) / s on the voxels with x > *thr (all when thr is NULL; the others are copied); clip = 0 skips the clip.  mean and std are
+ * stats[1], stats[2] rounded to fp32 when stats is given, else the two floats.  policy 0: s = max(std, floor) (the reference's max(std, 1e-8)); policy 1:
+ * s = std, or 1 when std == 0 (MONAI NormalizeIntensity).  fp32 subtraction and IEEE division.  out may be x itself (no other overlap). */
+int vx_normalize_apply(const float* x, float* out, long n, const float* thr, const double* stats, float mean, float std, int clip, float lo, float hi,
+                       int policy, float floor, void* stream);
+/* Radix-select histogram.  key(x) = float bits with the sign bit flipped for x >= +0 and every bit flipped otherwise: unsigned order of the keys = order of the
+ * floats (-0 below +0).  Over the selected voxels (mask > 0; mask NULL = all) whose key starts with the prefix_bits-bit `prefix`, hist[(key >> shift) & (2^bin_bits
+ * - 1)] += 1 with shift = 32 - prefix_bits - bin_bits; 1 <= bin_bits <= 11, 0 <= prefix_bits, prefix_bits + bin_bits <= 32.  Counts are aggregated in LDS
+ * and only non-zero bins leave a block, with one 64-bit integer atomic each; hist is ADDED to (the caller zeroes it; several volumes accumulate).  When given,
+ * minmax_key[0] / [1] take the min / max key over the selected non-NaN voxels (presets 0xffffffff / 0) and nan_count[0] is increased by the selected NaNs. */
+int vx_key_histogram(const float* x, const void* mask, int mask_bytes, long n, long prefix, int prefix_bits, int bin_bits, unsigned long long* hist,
+                     unsigned int* minmax_key, unsigned long long* nan_count, void* stream);
+/* Separable resampling of (C, D, H, W) to (C, Do, Ho, Wo).  The tables hold Do + Ho + Wo entries (z, then y, then x): for output index j of an axis the input
+ * indices i0[j], i1[j] and the weight w[j] of i1; indices are clamped to the axis in the kernel.  mode 0: three nested lerps a + w (b - a) (fmaf) in the order x, y, z,
+ * all fp32.  mode 1: gather through i0 (i1 and w may be NULL).  out must not alias x.  The label variant copies elements of 1 / 4 / 8 bytes (code -4 = 4) bit for bit. */
+int vx_resample_axes(const float* x, float* out, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, const int* i1, const float* w, int mode, void* stream);
+int vx_resample_axes_label(const void* x, void* out, int lab_bytes, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, void* stream);
+
 /* ---- dense strided convolution on MFMA (groups = 1; k odd <= 7, stride 2..4, pad = k / 2): the DownConv layers between the encoder levels and the
  * stem (Encoder.py:29-58, conv_blocks.py:8-27 of the reference).  Implicit GEMM on v_mfma_f32_16x16x4_f32, fp32 in / fp32 accumulate.  ws =
  * vx_conv_mfma_ws_floats(Cin, Cout, K, backward) floats for the operand-order weight image (written by every call).  bwd_data: accumulate = 1 adds

@@ -32,7 +32,8 @@ def _need_cuda(t, what):
         raise ValueError(f"{what}: expected (C, D, H, W), got {tuple(t.shape)}")
 
 
-def _label_code(lab):
+def label_code(lab):
+    """bytes code of a label / mask tensor for the C entries: uint8 1, int32 4, int64 8, float32 -4"""
     code = {torch.uint8: 1, torch.int32: 4, torch.int64: 8, torch.float32: -4}.get(lab.dtype)
     if code is None:
         raise TypeError(f"label dtype {lab.dtype} not supported (uint8, int32, int64, float32)")
@@ -63,7 +64,7 @@ class _LabelIndex:
         if label.shape[0] != 1:
             raise ValueError("label must have one channel")
         self.lab = label.contiguous()
-        self.code = _label_code(self.lab)
+        self.code = label_code(self.lab)
         self.n = self.lab.numel()
         nb = (self.n + _CHUNK - 1) // _CHUNK
         cnt = torch.empty(nb, dtype=torch.int32, device=label.device)
