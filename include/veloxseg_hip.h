@@ -574,6 +574,27 @@ int vx_key_histogram(const float* x, const void* mask, int mask_bytes, long n, l
 int vx_resample_axes(const float* x, float* out, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, const int* i1, const float* w, int mode, void* stream);
 int vx_resample_axes_label(const void* x, void* out, int lab_bytes, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, void* stream);
 
+/* ---- connected components (csrc/components.hip): labelling, per-component tallies, keep / drop filter ------------------------------
+ * No counterpart in the reference (its metrics are per voxel).  One sample per call; label maps are uint8 / int32 / int64 (bytes 1 / 4 / 8, compared as raw
+ * values), component maps int32.  Integer work only: equal inputs give equal bits.
+ *
+ * vx_cc_label: two voxels are joined when they are neighbours under `connectivity` (6 / 18 / 26: offsets in {-1, 0, 1}^3 with 1 / <= 2 / <= 3 non-zero
+ * coordinates) and hold the SAME NON-ZERO value.  cc[v] = 0 where labels[v] == 0, else the component's id in 1..N; components are numbered by ascending smallest
+ * flat index (z slowest, x fastest: scipy.ndimage.label's order); num[0] = N.  cc serves as the union-find parent array; ws holds vx_cc_ws_bytes(D, H, W) bytes
+ * (8-byte aligned; written by every call, no zero-fill needed).  D * H * W <= 2^31 - 1; anything larger, another connectivity or label width is refused and
+ * nothing is written.  Seven launches (unions inside 8 x 8 x 32 LDS tiles, unions across the tile faces in the global array, roots, three for the prefix sum,
+ * ids), no cross-workgroup waiting.  vx_cc_grid_cap() = the block count above which the kernels over tiles and voxels loop
+ * (the prefix sum runs one block per chunk of 262144 voxels, one block over the at most 8192 chunk sums). */
+int vx_cc_ws_bytes(int D, int H, int W);
+int vx_cc_grid_cap(void);
+int vx_cc_label(const void* labels, int lab_bytes, int* cc, int D, int H, int W, int connectivity, void* ws, int* num, void* stream);
+/* sizes[id] += 1 and hits[id] += (other[v] != 0) over the V voxels of a component map with ids in 0..N (id 0 = background is tallied too; ids outside 0..N are
+ * skipped); both arrays hold N + 1 counts and are ADDED to (the caller zeroes them).  other and hits are given together or both NULL.  Counts are gathered per wave
+ * (ballots) and per block (LDS) first; what leaves a block is one 64-bit integer atomic per id it met, or per run of equal ids where its LDS table is taken. */
+int vx_cc_tally(const int* cc, const void* other, int other_bytes, long V, int N, unsigned long long* sizes, unsigned long long* hits, void* stream);
+/* out[v] = keep[cc[v]] ? in[v] : 0 (keep: N + 1 bytes; an id outside 0..N is dropped); in / out of lab_bytes 1 / 4 / 8; out may be in itself */
+int vx_cc_select(const int* cc, const unsigned char* keep, int N, const void* in, void* out, int lab_bytes, long V, void* stream);
+
 /* ---- dense strided convolution on MFMA (groups = 1; k odd <= 7, stride 2..4, pad = k / 2): the DownConv layers between the encoder levels and the
  * stem (Encoder.py:29-58, conv_blocks.py:8-27 of the reference).  Implicit GEMM on v_mfma_f32_16x16x4_f32, fp32 in / fp32 accumulate.  ws =
  * vx_conv_mfma_ws_floats(Cin, Cout, K, backward) floats for the operand-order weight image (written by every call).  bwd_data: accumulate = 1 adds

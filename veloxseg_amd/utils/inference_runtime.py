@@ -212,8 +212,10 @@ class Net(torch.nn.Module):
 
 
 @torch.inference_mode()
-def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, overlap: float, taped: bool = True):
+def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, overlap: float, taped: bool = True, postprocess=None):
     """eval-mode sliding-window segmentation of one (B, C, D, H, W) volume -> (blended logits, uint8 label map).
+    postprocess (a utils.components.Postprocess, or the dict its from_config takes): the returned label map is the cleaned-up one (components below a voxel
+    count dropped / the k largest kept, on the GPU); the returned logits are untouched.
     taped (default): the forward of a full window batch is captured once per model and replayed as a launch tape (engine.TapedPredictor); the result
     is the eager forward's (checked at capture).  The accumulator of the blending reads the predictor's static output before the next replay
     overwrites it (same stream).  The predictor hangs on the model object (no process-wide cache, nothing outlives the model) and re-captures
@@ -231,6 +233,10 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
             if pred is None:
                 pred = TapedPredictor(net)
                 model.__dict__["_vx_taped_predictor"] = pred       # plain attribute (not a sub-module): dies with the model
-        return sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True)
+        logits, labels = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True)
+        if postprocess is not None:
+            from .components import Postprocess
+            labels = (postprocess if isinstance(postprocess, Postprocess) else Postprocess.from_config(postprocess))(labels)
+        return logits, labels
     finally:
         model.train(was_training)
