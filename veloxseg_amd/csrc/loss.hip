@@ -169,40 +169,70 @@ __global__ void vx_loss_finalize_k(const double* __restrict__ acc, int nh, int B
                                    const float* __restrict__ gs, const float* __restrict__ g0, const float* __restrict__ g1,
                                    const float* __restrict__ g2, const float* __restrict__ g3, int M, int Cg, float w_f,
                                    float* __restrict__ loss_out, float* __restrict__ coef) {
-    // Gram (SDKT) term: the only O(B*Cg*Cg) part -- all 64 lanes share it, lane 0 then does the scalar bookkeeping
+    // Gram (SDKT) term: the only O(B*Cg*Cg) part -- all 64 lanes share it.  Then one lane per (head, b, c) cell: its two coefficients and its Dice term (the fp64
+    // divisions and the dependent loads of 32 cells ran on lane 0 alone: 22 us with the chip idle); lane 0 adds the Dice terms from LDS in the order of the serial
+    // loop and does the scalar bookkeeping, so loss_out and every coefficient keep their bits.
+    constexpr int VX_FIN_CELLS = 512;                   // Dice terms held in LDS; lane 0 forms the terms of any further cell itself (same expression)
+    __shared__ double dterm[VX_FIN_CELLS];
+    __shared__ double hw[4], hce[4];                    // per head: its weight and its cross-entropy mean, loaded by lane h
     double feat = 0.0;
     const long ng = (long)B * Cg * Cg;
     if (gs && M > 0) {
         const float* gm_[4] = {g0, g1, g2, g3};
         for (int m = 0; m < M; ++m) {
             double s_ = 0.0;
+#pragma unroll 8                                       // eight pairs of loads in flight; the additions keep their order
             for (long i = threadIdx.x; i < ng; i += 64) { const double d = (double)gs[i] - (double)gm_[m][i]; s_ += d * d; }
             feat += vx_wave_sum(s_) / (double)ng;
         }
     }
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (blockIdx.x != 0) return;
     const double eps = 1e-5;
+    const long BCc = (long)B * C, ncell = (long)nh * BCc;
+    for (long cell = threadIdx.x; cell < ncell; cell += 64) {
+        const int h = (int)(cell / BCc);
+        const long bc = cell - (long)h * BCc;
+        const int c = (int)(bc % C);
+        const double* ah = acc + (long)h * (1 + BCc * 3);
+        float* ch = coef + (long)h * (1 + BCc * 2);
+        const double w = (double)wds[h];
+        const double wd = w / ((double)B * (double)(C - 1));
+        const double I = ah[1 + bc * 3], P = ah[2 + bc * 3], T = ah[3 + bc * 3];
+        const double U = P + T + eps;
+        float al = 0.0f, be = 0.0f;
+        double term = 0.0;
+        if (c >= 1) {
+            term = 1.0 - (2.0 * I + eps) / U;
+            al = (float)(-2.0 * wd / U);
+            be = (float)(wd * (2.0 * I + eps) / (U * U));
+        }
+        if (cell < VX_FIN_CELLS) dterm[cell] = term;
+        ch[1 + bc * 2] = al;
+        ch[2 + bc * 2] = be;
+    }
+    if ((int)threadIdx.x < nh) {
+        const int h = threadIdx.x;
+        const double w = (double)wds[h];
+        hw[h] = w;
+        hce[h] = acc[(long)h * (1 + BCc * 3)] / ((double)B * (double)V);
+        coef[(long)h * (1 + BCc * 2)] = (float)(w / ((double)B * (double)V));
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
     double total = 0.0;
     for (int h = 0; h < nh; ++h) {
-        const double* ah = acc + (long)h * (1 + (long)B * C * 3);
-        float* ch = coef + (long)h * (1 + (long)B * C * 2);
-        const double w = (double)wds[h];
-        const double ce = ah[0] / ((double)B * (double)V);
+        const double* ah = acc + (long)h * (1 + BCc * 3);
+        const double w = hw[h], ce = hce[h];
         double dice = 0.0;
-        const double wd = w / ((double)B * (double)(C - 1));
-        ch[0] = (float)(w / ((double)B * (double)V));
         for (int b = 0; b < B; ++b)
-            for (int c = 0; c < C; ++c) {
-                const double I = ah[1 + ((long)b * C + c) * 3], P = ah[2 + ((long)b * C + c) * 3], T = ah[3 + ((long)b * C + c) * 3];
-                const double U = P + T + eps;
-                float al = 0.0f, be = 0.0f;
-                if (c >= 1) {
+            for (int c = 1; c < C; ++c) {
+                const long bc = (long)b * C + c, cell = (long)h * BCc + bc;
+                if (cell < VX_FIN_CELLS) dice += dterm[cell];
+                else {
+                    const double I = ah[1 + bc * 3], P = ah[2 + bc * 3], T = ah[3 + bc * 3];
+                    const double U = P + T + eps;
                     dice += 1.0 - (2.0 * I + eps) / U;
-                    al = (float)(-2.0 * wd / U);
-                    be = (float)(wd * (2.0 * I + eps) / (U * U));
                 }
-                ch[1 + ((long)b * C + c) * 2] = al;
-                ch[2 + ((long)b * C + c) * 2] = be;
             }
         dice /= (double)B * (double)(C - 1);
         total += w * (ce + dice);
@@ -331,52 +361,107 @@ __global__ void __launch_bounds__(256) vx_gram_mse_bwd_k(const float* __restrict
 // ---------------------------------------------------------------------------------------------
 // Gram matrix G[b,m,n] = sum_v x[b,m,v] x[b,n,v] / (C*V)    (C <= 32)
 // ---------------------------------------------------------------------------------------------
-#define VX_GT 64
-__global__ void __launch_bounds__(256) vx_gram_fwd_k(const float* __restrict__ x, float* __restrict__ G, int C, long V, int tiles_per_block) {
-    __shared__ float tile[32][VX_GT + 1];
+// forward on the fp32 matrix pipe: x x^T over 4 voxels is ONE v_mfma_f32_16x16x4_f32 whose A and B operands are the same register (A lane = (row l%16, k l/16),
+// B lane = (k l/16, col l%16): both are x[channel l%16][voxel k]).  A lane loads 16 bytes = 4 voxels of its channel row, which feed 4 chained MFMAs (the voxel <-> k
+// assignment is free under the sum).  Was: 4-byte staging into LDS and 64 LDS-fed FMAs per pair with two LDS reads each, and 1024 blocks x C^2 atomics.
+// block = 4 waves x 256 voxels; the waves' tiles meet in LDS, then one atomic per (m, n) and block;  . 1/(C V) after the block's sum.
+#define VX_GB 1024                  // voxels per block
+#define VX_GMFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+typedef float vx_gf4 __attribute__((ext_vector_type(4)));
+template <int NT>                   // row groups of 16 channels: 1 (C <= 16) or 2 (C <= 32)
+__global__ void __launch_bounds__(256) vx_gram_fwd_k(const float* __restrict__ x, float* __restrict__ G, int C, long V, int al) {
+    __shared__ float red[4][NT * NT * 256];
     const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int r = lane & 15, q = lane >> 4;
     const float* __restrict__ xb = x + (long)b * C * V;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    const long v_begin = (long)blockIdx.x * tiles_per_block * VX_GT;
-    for (int tl = 0; tl < tiles_per_block; ++tl) {
-        const long v0 = v_begin + (long)tl * VX_GT;
-        if (v0 >= V) break;
-        __syncthreads();
-        for (int e = threadIdx.x; e < C * VX_GT; e += 256) {
-            const int c = e / VX_GT, k = e % VX_GT;
-            tile[c][k] = (v0 + k < V) ? xb[(long)c * V + v0 + k] : 0.0f;
+    vx_gf4 acc[NT][NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = (vx_gf4){0.f, 0.f, 0.f, 0.f};
+    const long vb = (long)blockIdx.x * VX_GB + wid * (VX_GB / 4);
+#pragma unroll
+    for (int t = 0; t < VX_GB / 4 / 16; ++t) {
+        const long v = vb + t * 16 + q * 4;
+        float a[NT][4];
+#pragma unroll
+        for (int g = 0; g < NT; ++g) {
+            const int c = 16 * g + r;
+            a[g][0] = a[g][1] = a[g][2] = a[g][3] = 0.0f;
+            if (c < C && v < V) {
+                const float* __restrict__ p = xb + (long)c * V + v;
+                if (al) { const float4 t4 = *reinterpret_cast<const float4*>(p); a[g][0] = t4.x; a[g][1] = t4.y; a[g][2] = t4.z; a[g][3] = t4.w; }      // al: V % 4 == 0
+                else {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (v + u < V) a[g][u] = p[u];
+                }
+            }
         }
-        __syncthreads();
-        int slot = 0;
-        for (int pr = threadIdx.x; pr < C * C; pr += 256, ++slot) {
-            const int m = pr / C, n = pr % C;
-            float s = 0.0f;
-#pragma unroll 8
-            for (int k = 0; k < VX_GT; ++k) s = fmaf(tile[m][k], tile[n][k], s);
-            acc[slot] += s;
-        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) acc[i][j] = VX_GMFMA(a[i][u], a[j][u], acc[i][j]);
     }
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) red[wid][(i * NT + j) * 256 + e * 64 + lane] = acc[i][j][e];
+    __syncthreads();
     const float norm = 1.0f / ((float)C * (float)V);
-    int slot = 0;
-    for (int pr = threadIdx.x; pr < C * C; pr += 256, ++slot) atomicAdd(G + (long)b * C * C + pr, acc[slot] * norm);
+    for (int e = threadIdx.x; e < NT * NT * 256; e += 256) {
+        const float s = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+        const int tile = e >> 8, i = (e >> 6) & 3, l = e & 63;              // D reg i of lane l = (row 4 (l / 16) + i, col l % 16)
+        const int m = 16 * (tile / NT) + 4 * (l >> 4) + i, n = 16 * (tile % NT) + (l & 15);
+        if (m < C && n < C) atomicAdd(G + (long)b * C * C + m * C + n, s * norm);
+    }
 }
 
 // dx[b,m,v] = sum_n (dG[b,m,n] + dG[b,n,m]) x[b,n,v] / (C*V)
-__global__ void __launch_bounds__(256) vx_gram_bwd_k(const float* __restrict__ x, const float* __restrict__ dG, float* __restrict__ dx, int C, long V) {
+// The symmetrised dG + dG^T of the sample sits in LDS once per block (was: both triangles re-read from global memory for every output channel: 2 C^2 loads per thread);
+// a thread owns VEC = 4 consecutive voxels: 16-byte loads of the C rows, 16-byte stores; n ascending in one fmaf chain, as before.  CT: compile-time C (0: run time).
+template <int CT, int VEC>
+__global__ void __launch_bounds__(128) vx_gram_bwd_k(const float* __restrict__ x, const float* __restrict__ dG, float* __restrict__ dx, int Crt, long V) {
+    __shared__ __attribute__((aligned(16))) float sym[32 * 32];
+    const int C = CT ? CT : Crt;
     const int b = blockIdx.y;
-    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    const float* __restrict__ gb = dG + (long)b * C * C;
+    for (int e = threadIdx.x; e < C * C; e += 128) { const int m = e / C, n = e % C; sym[e] = gb[m * C + n] + gb[n * C + m]; }
+    __syncthreads();
+    const long v = ((long)blockIdx.x * 128 + threadIdx.x) * VEC;
     if (v >= V) return;
     const float* __restrict__ xb = x + (long)b * C * V + v;
-    const float* __restrict__ gb = dG + (long)b * C * C;
+    float* __restrict__ ob = dx + (long)b * C * V + v;
     const float norm = 1.0f / ((float)C * (float)V);
-    float xv[32];
+    float xv[32][VEC];
 #pragma unroll
-    for (int n = 0; n < 32; ++n) xv[n] = (n < C) ? xb[(long)n * V] : 0.0f;
+    for (int n = 0; n < 32; ++n) {
+        if (n < C) {
+            if (VEC == 4) { const float4 t = *reinterpret_cast<const float4*>(xb + (long)n * V); xv[n][0] = t.x; xv[n][1 % VEC] = t.y; xv[n][2 % VEC] = t.z; xv[n][3 % VEC] = t.w; }
+            else xv[n][0] = xb[(long)n * V];
+        } else {
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) xv[n][u] = 0.0f;
+        }
+    }
+#pragma unroll 2
     for (int m = 0; m < C; ++m) {
-        float s = 0.0f;
+        float s[VEC];
 #pragma unroll
-        for (int n = 0; n < 32; ++n) if (n < C) s = fmaf(gb[m * C + n] + gb[n * C + m], xv[n], s);
-        dx[(long)b * C * V + (long)m * V + v] = s * norm;
+        for (int u = 0; u < VEC; ++u) s[u] = 0.0f;
+        const float* __restrict__ gr = sym + m * C;
+#pragma unroll
+        for (int n = 0; n < 32; ++n) if (n < C) {
+            const float g = gr[n];
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) s[u] = fmaf(g, xv[n][u], s[u]);
+        }
+        if (VEC == 4) *reinterpret_cast<float4*>(ob + (long)m * V) = make_float4(s[0] * norm, s[1 % VEC] * norm, s[2 % VEC] * norm, s[3 % VEC] * norm);
+        else ob[(long)m * V] = s[0] * norm;
     }
 }
 
@@ -705,17 +790,23 @@ extern "C" int vx_gram_fwd(const float* x, float* G, int B, int C, long V, void*
     VX_REQUIRE(x && G && B > 0 && C > 0 && C <= 32 && V > 0, "vx_gram_fwd: bad args (C <= 32)");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(G, 0, sizeof(float) * (size_t)B * C * C, st) != hipSuccess) VX_FAIL(-2, "vx_gram_fwd: memset failed");
-    const long tiles = (V + VX_GT - 1) / VX_GT;
-    int tpb = (int)((tiles + 255) / 256);
-    if (tpb < 1) tpb = 1;
-    hipLaunchKernelGGL(vx_gram_fwd_k, dim3(vx_cdiv(tiles, tpb), B), dim3(256), 0, st, x, G, C, V, tpb);
+    const int al = ((V & 3) == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
+    const dim3 grid(vx_cdiv(V, VX_GB), B);
+    if (C <= 16) hipLaunchKernelGGL(vx_gram_fwd_k<1>, grid, dim3(256), 0, st, x, G, C, V, al);
+    else hipLaunchKernelGGL(vx_gram_fwd_k<2>, grid, dim3(256), 0, st, x, G, C, V, al);
     VX_LAUNCH_CHECK("vx_gram_fwd");
     return 0;
 }
 
 extern "C" int vx_gram_bwd(const float* x, const float* dG, float* dx, int B, int C, long V, void* stream) {
     VX_REQUIRE(x && dG && dx && B > 0 && C > 0 && C <= 32 && V > 0, "vx_gram_bwd: bad args (C <= 32)");
-    hipLaunchKernelGGL(vx_gram_bwd_k, dim3(vx_cdiv(V, 256), B), dim3(256), 0, (hipStream_t)stream, x, dG, dx, C, V);
+    hipStream_t st = (hipStream_t)stream;
+    if ((V & 3) == 0 && ((((uintptr_t)x | (uintptr_t)dx) & 15) == 0)) {
+        const dim3 grid(vx_cdiv(V / 4, 128), B);
+        if (C == 16) hipLaunchKernelGGL((vx_gram_bwd_k<16, 4>), grid, dim3(128), 0, st, x, dG, dx, C, V);
+        else if (C == 32) hipLaunchKernelGGL((vx_gram_bwd_k<32, 4>), grid, dim3(128), 0, st, x, dG, dx, C, V);
+        else hipLaunchKernelGGL((vx_gram_bwd_k<0, 4>), grid, dim3(128), 0, st, x, dG, dx, C, V);
+    } else hipLaunchKernelGGL((vx_gram_bwd_k<0, 1>), dim3(vx_cdiv(V, 128), B), dim3(128), 0, st, x, dG, dx, C, V);
     VX_LAUNCH_CHECK("vx_gram_bwd");
     return 0;
 }

@@ -316,10 +316,33 @@ __global__ void __launch_bounds__(256) vx_in_stats_part3_k(VxIn3 P, double* __re
     }
 }
 
+// The two consumers stream VX_IN_SPAN elements of a row per block (was 256: 8192 blocks that each folded the partials in front of one element per thread): a thread
+// owns four quads, 256 quads apart, and issues all its 16-byte loads BEFORE the fold, so the fp64 fold (S additions, a division, a square root) runs under the loads'
+// latency and once per 4096 elements.  The fold, the (mean, rstd) store and the per-element expression are those of the separate-launch kernels (bit-identical results).
+// Rows that do not start on a 16-byte boundary (V % 4 != 0, or an unaligned base) take the scalar path; the last V % 4 elements of an aligned row are scalar too.
+#define VX_IN_SPAN 4096
+__device__ __forceinline__ bool vx_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
 __global__ void __launch_bounds__(256) vx_in_apply_fwd_fin_k(VxIn3 P, const double* __restrict__ part, int S, float eps, int nk, int act,
                                                              const float* __restrict__ res, float* __restrict__ out, long BC, long V) {
     __shared__ float ms[6];
     const long bc = blockIdx.y;
+    const long row = bc * V, v0 = (long)blockIdx.x * VX_IN_SPAN;
+    bool vec = (row & 3) == 0 && vx_al16(out) && vx_al16(res);
+    for (int k = 0; k < nk; ++k) vec = vec && vx_al16(P.y[k]);
+    float4 yq[3][4], rq[4];
+    if (vec) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long v = v0 + ((long)j * 256 + threadIdx.x) * 4;
+            rq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (v + 3 < V) {
+                if (res) rq[j] = *reinterpret_cast<const float4*>(res + row + v);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) if (k < nk) yq[k][j] = *reinterpret_cast<const float4*>(P.y[k] + row + v);
+            }
+        }
+    }
     if ((int)threadIdx.x < nk) {
         const int k = threadIdx.x;
         const double* __restrict__ pp = part + (((long)k * BC + bc) * S) * 2;
@@ -333,15 +356,45 @@ __global__ void __launch_bounds__(256) vx_in_apply_fwd_fin_k(VxIn3 P, const doub
         if (blockIdx.x == 0) { P.st[k][2 * bc] = mean; P.st[k][2 * bc + 1] = rstd; }
     }
     __syncthreads();
-    const long v = (long)blockIdx.x * 256 + threadIdx.x;
-    if (v >= V) return;
-    const long i = bc * V + v;
-    float acc = res ? res[i] : 0.0f;
-    for (int k = 0; k < nk; ++k) {
-        const float z = (P.y[k][i] - ms[2 * k]) * ms[2 * k + 1];
-        acc += act ? vx_gelu(z) : z;
+    if (!vec) {
+        for (long v = v0 + threadIdx.x; v < v0 + VX_IN_SPAN && v < V; v += 256) {
+            const long i = row + v;
+            float acc = res ? res[i] : 0.0f;
+            for (int k = 0; k < nk; ++k) {
+                const float z = (P.y[k][i] - ms[2 * k]) * ms[2 * k + 1];
+                acc += act ? vx_gelu(z) : z;
+            }
+            out[i] = acc;
+        }
+        return;
     }
-    out[i] = acc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long v = v0 + ((long)j * 256 + threadIdx.x) * 4;
+        if (v + 3 < V) {
+            float acc[4] = {rq[j].x, rq[j].y, rq[j].z, rq[j].w};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) if (k < nk) {
+                const float yv[4] = {yq[k][j].x, yq[k][j].y, yq[k][j].z, yq[k][j].w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float z = (yv[u] - ms[2 * k]) * ms[2 * k + 1];
+                    acc[u] += act ? vx_gelu(z) : z;
+                }
+            }
+            *reinterpret_cast<float4*>(out + row + v) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        } else {
+            for (long e = v; e < V; ++e) {                 // the last V % 4 elements of the row
+                const long i = row + e;
+                float acc = res ? res[i] : 0.0f;
+                for (int k = 0; k < nk; ++k) {
+                    const float z = (P.y[k][i] - ms[2 * k]) * ms[2 * k + 1];
+                    acc += act ? vx_gelu(z) : z;
+                }
+                out[i] = acc;
+            }
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) vx_in_bwd_stats_part3_k(const float* __restrict__ dout, VxIn3 P, int act, double* __restrict__ part, long BC, long V, int S) {
@@ -377,6 +430,23 @@ __global__ void __launch_bounds__(256) vx_in_bwd_apply_fin_k(const float* __rest
     const long bc = blockIdx.y;
     const int k = blockIdx.z;
     if (P.dy[k] == nullptr) return;
+    const float* __restrict__ y = P.y[k];
+    float* __restrict__ dy = P.dy[k];
+    const float* __restrict__ ad = k == 0 ? add0 : nullptr;
+    const long row = bc * V, v0 = (long)blockIdx.x * VX_IN_SPAN;
+    const bool vec = (row & 3) == 0 && vx_al16(dout) && vx_al16(y) && vx_al16(dy) && vx_al16(ad);
+    float4 yq[4], dq[4], aq[4];
+    if (vec) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long v = v0 + ((long)j * 256 + threadIdx.x) * 4;
+            if (v + 3 < V) {
+                yq[j] = *reinterpret_cast<const float4*>(y + row + v);
+                dq[j] = *reinterpret_cast<const float4*>(dout + row + v);
+                if (ad) aq[j] = *reinterpret_cast<const float4*>(ad + row + v);
+            }
+        }
+    }
     if (threadIdx.x == 0) {
         const double* __restrict__ pp = part + (((long)k * BC + bc) * S) * 2;
         double a = 0.0, c = 0.0;
@@ -384,14 +454,42 @@ __global__ void __launch_bounds__(256) vx_in_bwd_apply_fin_k(const float* __rest
         mm[0] = (float)(a / (double)V); mm[1] = (float)(c / (double)V);
     }
     __syncthreads();
-    const long v = (long)blockIdx.x * 256 + threadIdx.x;
-    if (v >= V) return;
-    const long i = bc * V + v;
     const float mean = P.st[k][2 * bc], rstd = P.st[k][2 * bc + 1];
-    const float z = (P.y[k][i] - mean) * rstd;
-    const float dz = act ? dout[i] * vx_gelu_grad(z) : dout[i];
-    const float o = rstd * (dz - mm[0] - z * mm[1]);
-    P.dy[k][i] = (k == 0 && add0) ? add0[i] + o : o;
+    if (!vec) {
+        for (long v = v0 + threadIdx.x; v < v0 + VX_IN_SPAN && v < V; v += 256) {
+            const long i = row + v;
+            const float z = (y[i] - mean) * rstd;
+            const float dz = act ? dout[i] * vx_gelu_grad(z) : dout[i];
+            const float o = rstd * (dz - mm[0] - z * mm[1]);
+            dy[i] = ad ? ad[i] + o : o;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long v = v0 + ((long)j * 256 + threadIdx.x) * 4;
+        if (v + 3 < V) {
+            const float yv[4] = {yq[j].x, yq[j].y, yq[j].z, yq[j].w}, dv[4] = {dq[j].x, dq[j].y, dq[j].z, dq[j].w};
+            float av[4] = {0.f, 0.f, 0.f, 0.f}, ov[4];
+            if (ad) { av[0] = aq[j].x; av[1] = aq[j].y; av[2] = aq[j].z; av[3] = aq[j].w; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float z = (yv[u] - mean) * rstd;
+                const float dz = act ? dv[u] * vx_gelu_grad(z) : dv[u];
+                const float o = rstd * (dz - mm[0] - z * mm[1]);
+                ov[u] = ad ? av[u] + o : o;
+            }
+            *reinterpret_cast<float4*>(dy + row + v) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+        } else {
+            for (long e = v; e < V; ++e) {                 // the last V % 4 elements of the row
+                const long i = row + e;
+                const float z = (y[i] - mean) * rstd;
+                const float dz = act ? dout[i] * vx_gelu_grad(z) : dout[i];
+                const float o = rstd * (dz - mm[0] - z * mm[1]);
+                dy[i] = ad ? ad[i] + o : o;
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -449,7 +547,7 @@ extern "C" int vx_in_fwd_split(const float* y0, const float* y1, const float* y2
     const int S = vx_in_split(BC, V);
     VxIn3 P; P.y[0] = y0; P.y[1] = y1; P.y[2] = y2; P.st[0] = s0; P.st[1] = s1; P.st[2] = s2; P.dy[0] = P.dy[1] = P.dy[2] = nullptr;
     hipLaunchKernelGGL(vx_in_stats_part3_k, dim3((unsigned)BC, S, nk), dim3(256), 0, (hipStream_t)stream, P, part_ws, BC, V, S);
-    hipLaunchKernelGGL(vx_in_apply_fwd_fin_k, dim3(vx_cdiv(V, 256), (unsigned)BC), dim3(256), 0, (hipStream_t)stream, P, (const double*)part_ws, S, eps, nk, act, res, out, BC, V);
+    hipLaunchKernelGGL(vx_in_apply_fwd_fin_k, dim3(vx_cdiv(V, VX_IN_SPAN), (unsigned)BC), dim3(256), 0, (hipStream_t)stream, P, (const double*)part_ws, S, eps, nk, act, res, out, BC, V);
     VX_LAUNCH_CHECK("vx_in_fwd_split");
     return 0;
 }
@@ -463,7 +561,7 @@ extern "C" int vx_in_bwd_split(const float* dout, const float* y0, const float* 
     VxIn3 P; P.y[0] = y0; P.y[1] = y1; P.y[2] = y2; P.st[0] = const_cast<float*>(s0); P.st[1] = const_cast<float*>(s1); P.st[2] = const_cast<float*>(s2);
     P.dy[0] = dy0; P.dy[1] = nk > 1 ? dy1 : nullptr; P.dy[2] = nk > 2 ? dy2 : nullptr;
     hipLaunchKernelGGL(vx_in_bwd_stats_part3_k, dim3((unsigned)BC, S, nk), dim3(256), 0, (hipStream_t)stream, dout, P, act, part_ws, BC, V, S);
-    hipLaunchKernelGGL(vx_in_bwd_apply_fin_k, dim3(vx_cdiv(V, 256), (unsigned)BC, nk), dim3(256), 0, (hipStream_t)stream, dout, P, (const double*)part_ws, S, act, BC, V, add0);
+    hipLaunchKernelGGL(vx_in_bwd_apply_fin_k, dim3(vx_cdiv(V, VX_IN_SPAN), (unsigned)BC, nk), dim3(256), 0, (hipStream_t)stream, dout, P, (const double*)part_ws, S, act, BC, V, add0);
     VX_LAUNCH_CHECK("vx_in_bwd_split");
     return 0;
 }
