@@ -380,6 +380,8 @@ int vx_pwa_scatter_bwd_all_w(const float* const* douts, float* dtok, const VxPwa
 int vx_pwa_scatter_bwd_all_wz(const float* const* douts, float* dtok, const VxPwaPlan* plan, int c, int M, int B, float* extra_zero, long extra_floats, void* stream);
 int vx_pwa_attn_set_fused_bwd(int on); /* A/B knob: 1 (default) = the dQ and dK/dV passes of vx_pwa_attn_bwd share one launch (interleaved blocks), 0 = two launches */
 int vx_pwa_scatter_set_ident(int on);   /* A/B knob: 1 (default) = 1x1x1 small windows take the transpose kernel, 0 = always the general adjoint */
+int vx_pwa_scatter_set_merged(int on);  /* A/B knob: 1 (default) = vx_pwa_scatter_bwd_all / _all_w / _all_wz run every scale in one launch (each token element has one owning block:
+                                         * reproducible) where B * M >= 8, 2 = at any size, 0 = one launch per scale, the wide-cell scales adding with float atomics */
 /* MultiModal attention_operation (PWA.py:308-327) + relative bias (attention_utils.py:120-125); table = (Tsz, heads).
  * O: (B,heads,Ntot,M*l,cv); LSE: (B,heads,Ntot,M*l).  bwd: dtable += ; delta_ws = vx_pwa_attn_bwd_ws_floats(plan, B, M) floats
  * (row-sum workspace + replicated bias-gradient tables; contents need not be initialised). */
@@ -391,7 +393,8 @@ int vx_pwa_attn_bwd_ws_floats(const VxPwaPlan* plan, int B, int M);   /* answer,
  * the next attention backward of this host thread on that workspace skips its zeroing launch */
 int vx_pwa_attn_bwd_rep_offset(const VxPwaPlan* plan, int B, int M);
 int vx_pwa_attn_bwd_mark_rep_zeroed(const float* delta_ws);
-int vx_pwa_gather_set_vec(int on);   /* A/B knob for tests: 0 = the one-lane-per-(cell, channel) gather kernels instead of the channel-vectorised ones */
+int vx_pwa_gather_set_vec(int on);   /* A/B knob for tests: 0 = the one-lane-per-(cell, channel) gather kernels instead of the channel-vectorised ones; 1 = default;
+                                      * 2 = as 1, and vx_pwa_gather_all_bwd takes its four-voxels-per-thread kernel at every size (by default: large volumes only) */
 int vx_pwa_attn_bwd(const float* Q, const float* K, const float* V, const float* table, const float* O, const float* LSE,
                     const float* dO, float* dQ, float* dK, float* dV, float* dtable, float* delta_ws,
                     const VxPwaPlan* plan, int B, int M, int cq, int cv,

@@ -310,6 +310,68 @@ __global__ void __launch_bounds__(256) vx_pwa_gather_all_bwd_v_k(VxGatherPtrs pt
     }
 }
 
+// The same with FOUR consecutive voxels of a row per thread (W % 4 == 0, 16-byte aligned volumes): the kernel is a pure writer of 3 M volumes, so every channel is one
+// 16-byte store per lane (a wave instruction writes 1 KiB of rows) instead of four dword stores, and the token and its index are read once per CELL the four voxels
+// fall into: the row's divisions happen once per thread, the walk to the next cell along W is additions ((t2, W2) -> the next token or the next window's first one).
+template <int CH>
+__global__ void __launch_bounds__(256) vx_pwa_gather_all_bwd_v4_k(VxGatherPtrs ptrs, const float* __restrict__ dtq, const float* __restrict__ dtk, const float* __restrict__ dtv,
+                                                                  const int* __restrict__ iq, const int* __restrict__ ik, const int* __restrict__ iv,
+                                                                  VxPwaPlan P, int cq, int cv, int M) {
+    const int nchq = cq / CH, nchv = cv / CH, nchm = nchq > nchv ? nchq : nchv;
+    int y = blockIdx.y, chunk, a, i, kind;
+    y = vx_fdivmod(y, vx_fd(nchm), chunk);
+    y = vx_fdivmod(y, vx_fd(P.heads), a);
+    y = vx_fdivmod(y, vx_fd(P.nb), i);
+    const int m = vx_fdivmod(y, vx_fd(3), kind);
+    const int c = kind == 2 ? cv : cq;
+    if (chunk * CH >= c) return;
+    const int b = blockIdx.z;
+    float* __restrict__ dsrc = ptrs.dsrc[3 * m + kind];
+    const float* __restrict__ dtok = kind == 0 ? dtq : (kind == 1 ? dtk : dtv);
+    const int* __restrict__ tix = kind == 0 ? iq : (kind == 1 ? ik : iv);
+    const long V = (long)P.grid[0] * P.grid[1] * P.grid[2];
+    const long v = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (v >= V) return;
+    int x2, x1, x0;
+    vx_unflatten(v, P.grid[1], P.grid[2], V < (1 << 22), x0, x1, x2);
+    const int s2 = P.small[i][2], n2 = P.n[2];
+    int t0, t1, t2, r2;
+    const int W0 = vx_fdivmod(vx_fdiv(x0, vx_fd(P.small[i][0])), vx_fd(P.n[0]), t0);
+    const int W1 = vx_fdivmod(vx_fdiv(x1, vx_fd(P.small[i][1])), vx_fd(P.n[1]), t1);
+    const int W2 = vx_fdivmod(vx_fdivmod(x2, vx_fd(s2), r2), vx_fd(n2), t2);
+    const int N = P.woff[i] + (W0 * P.nwin[i][1] + W1) * P.nwin[i][2] + W2;
+    const int t = (t0 * P.n[1] + t1) * n2 + t2;
+    long ti = ((((long)b * P.heads + a) * P.Ntot + N) * ((long)M * P.l) + (long)m * P.l + t) * c + chunk * CH;
+    const long next_window = ((long)M * P.l - (n2 - 1)) * c;          // from the last token of a window's row to the first of the next window's
+    const int ch0 = (i * P.heads + a) * c + chunk * CH;
+    float* __restrict__ dc = dsrc + ((long)b * (P.nb * P.heads * c) + ch0) * V + v;
+    const bool ident = P.small[i][0] * P.small[i][1] * P.small[i][2] == 1;       // (see the forward: no indices for 1 x 1 x 1 cells)
+    float g[CH], out[CH][4];
+    int ix[CH];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j == 0 || r2 == 0) {                                        // voxel j opens a cell
+#pragma unroll
+            for (int k = 0; k < CH; k += 4) {
+                const float4 g4 = *reinterpret_cast<const float4*>(dtok + ti + k);
+                g[k] = g4.x; g[k + 1] = g4.y; g[k + 2] = g4.z; g[k + 3] = g4.w;
+                if (!ident) {
+                    const int4 i4 = *reinterpret_cast<const int4*>(tix + ti + k);
+                    ix[k] = i4.x; ix[k + 1] = i4.y; ix[k + 2] = i4.z; ix[k + 3] = i4.w;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < CH; ++k) out[k][j] = (ident || ix[k] == (int)v + j) ? g[k] : 0.0f;
+        if (++r2 == s2) {                                               // the next voxel is in the next cell along W
+            r2 = 0;
+            if (++t2 == n2) { t2 = 0; ti += next_window; } else ti += c;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) *reinterpret_cast<float4*>(dc + (long)k * V) = make_float4(out[k][0], out[k][1], out[k][2], out[k][3]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // scatter: per-window trilinear up-sampling (align_corners=True) of the n^3 window outputs
 // ---------------------------------------------------------------------------------------------
@@ -438,14 +500,16 @@ __global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_k(VxScPtrs ptrs, float
 // small window 1x1x1 (every shipped config: min_small_window_sizes = [[1,1,1]] * 4): the per-window resampling is the identity, so the adjoint
 // is a transpose of the window's (c, voxels) slab into its (tokens, c) rows -- staged through LDS (pitch c + 1), coalesced on both sides, no atomics.
 // One block = one (b, head, window); every element of the destination rows is written exactly once, which equals "+=" on the zeroed buffer.
-__global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_ident_k(VxScPtrs ptrs, float* __restrict__ dtok, VxPwaPlan P, int c, int m0, int M, int scale, int nx, VxScZero z) {
+// (The adjoint kernels of the three sole-owner kinds are __device__ bodies over a block coordinate (X, Y, Z) in a grid (GX, GY, .): their own __global__ kernels pass
+// blockIdx / gridDim, vx_pwa_scatter_bwd_merged_k passes the coordinate inside the block range of one scale.  vx_sacc: the block's dynamic LDS.)
+__device__ __forceinline__ void vx_scatter_bwd_ident_body(float* __restrict__ vx_sacc, const int X, const int Y, const int GX, const int GY,
+                                                          const VxScPtrs& ptrs, float* __restrict__ dtok, const VxPwaPlan& P, int c, int m0, int M, int scale, int nx, const VxScZero& z) {
     int bx;
-    const int mm = vx_fdivmod(blockIdx.x, vx_fd(nx), bx);
+    const int mm = vx_fdivmod(X, vx_fd(nx), bx);
     const int m = m0 + mm;
     const float* __restrict__ dout = ptrs.in[mm];
-    extern __shared__ __attribute__((aligned(16))) float vx_sacc[];      // [l][c + 1]
     int a;
-    const int b = vx_fdivmod(blockIdx.y, vx_fd(P.heads), a);
+    const int b = vx_fdivmod(Y, vx_fd(P.heads), a);
     const int i = scale;
     const int Nl = bx, N = P.woff[i] + Nl;
     const int n0 = P.n[0], n1 = P.n[1], n2 = P.n[2];
@@ -469,16 +533,20 @@ __global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_ident_k(VxScPtrs ptrs,
         for (int r = 0; r < z.n; ++r) {
             float* __restrict__ zb = dtok + (((long)b * P.heads + a) * P.Ntot + z.w0[r]) * ((long)M * l) * c;
             const long len = (long)z.wn[r] * M * l * c;
-            for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < len; k += (long)gridDim.x * 256) zb[k] = 0.0f;
+            for (long k = (long)X * 256 + threadIdx.x; k < len; k += (long)GX * 256) zb[k] = 0.0f;
         }
         if (z.extra != nullptr) {
             float4* __restrict__ e4 = reinterpret_cast<float4*>(z.extra);
-            const long nb = (long)gridDim.x * gridDim.y, bid = blockIdx.x + (long)gridDim.x * blockIdx.y;
+            const long nb = (long)GX * GY, bid = X + (long)GX * Y;
             for (long k = bid * 256 + threadIdx.x; k < z.extra_n4; k += nb * 256) e4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         return;
     }
     for (int k = threadIdx.x; k < l * c; k += 256) { int kc; const int kt = vx_fdivmod(k, fc, kc); dt[k] += vx_sacc[kt * pitch + kc]; }       // sole owner of these rows: "+=" without atomics
+}
+__global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_ident_k(VxScPtrs ptrs, float* __restrict__ dtok, VxPwaPlan P, int c, int m0, int M, int scale, int nx, VxScZero z) {
+    extern __shared__ __attribute__((aligned(16))) float vx_sacc[];      // [l][c + 1]
+    vx_scatter_bwd_ident_body(vx_sacc, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, ptrs, dtok, P, c, m0, M, scale, nx, z);
 }
 
 // General small window (2x2x2 .. 4x4x4): the adjoint as a GATHER, one block = one (window, b*head, channel).  Every token collects, per axis, the
@@ -486,15 +554,15 @@ __global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_ident_k(VxScPtrs ptrs,
 // staged in LDS; PT = 256 / l threads share a token (they split the outermost tap axis) and are summed with shuffles.  Replaces 8 scattered
 // ds_add_f32 per voxel of the atomic kernel below (45 us per launch at the second scale) by 8 LDS reads per voxel.
 #define VX_SC_TAPS 12
-__global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_gather_k(VxScPtrs ptrs, float* __restrict__ dtok, VxPwaPlan P, int c, int m0, int M, int scale, int PT, int nx, int assign) {
+__device__ __forceinline__ void vx_scatter_bwd_gather_body(float* __restrict__ vx_sacc, const int X, const int Y, const int Z,
+                                                           const VxScPtrs& ptrs, float* __restrict__ dtok, const VxPwaPlan& P, int c, int m0, int M, int scale, int PT, int nx, int assign) {
     int bx;
-    const int mm = vx_fdivmod(blockIdx.x, vx_fd(nx), bx);
+    const int mm = vx_fdivmod(X, vx_fd(nx), bx);
     const int m = m0 + mm;
     const float* __restrict__ dout = ptrs.in[mm];
-    extern __shared__ __attribute__((aligned(16))) float vx_sacc[];      // [nv] slab | taps
     int a;
-    const int b = vx_fdivmod(blockIdx.y, vx_fd(P.heads), a);
-    const int cc = blockIdx.z;
+    const int b = vx_fdivmod(Y, vx_fd(P.heads), a);
+    const int cc = Z;
     const int i = scale;
     const int Nl = bx, N = P.woff[i] + Nl;
     const int n0 = P.n[0], n1 = P.n[1], n2 = P.n[2];
@@ -553,6 +621,10 @@ __global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_gather_k(VxScPtrs ptrs
         for (int o = 1; o < PT; o <<= 1) acc += __shfl_xor(acc, o, 64);
         if (sub == 0) { if (assign) dt[(long)t * c] = acc; else dt[(long)t * c] += acc; }               // sole owner of this element: "+=" without atomics (assign: the destination was not zeroed)
     }
+}
+__global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_gather_k(VxScPtrs ptrs, float* __restrict__ dtok, VxPwaPlan P, int c, int m0, int M, int scale, int PT, int nx, int assign) {
+    extern __shared__ __attribute__((aligned(16))) float vx_sacc[];      // [nv] slab | taps
+    vx_scatter_bwd_gather_body(vx_sacc, blockIdx.x, blockIdx.y, blockIdx.z, ptrs, dtok, P, c, m0, M, scale, PT, nx, assign);
 }
 
 
@@ -639,6 +711,140 @@ __global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_sep_k(VxScPtrs ptrs, f
         const float v = acc[t];
         if (v != 0.0f) atomicAdd(dt + (long)t * c, v);
     }
+}
+
+// The same scales with a SOLE OWNER per token element, for the one-launch adjoint below (no block may wait for another there, so nothing can be zeroed for atomics
+// to add into).  One block = (window, b * head, channel, coarse plane t0, coarse row t1): it reads the fine rows whose D and H stencils touch (t0, t1) -- about
+// 2 (bw - 1) / (n - 1) per axis, so the window's box is read ~4 times, from L2 -- as consecutive 16-byte pieces (VW = 4; a wave instruction covers whole rows of the box),
+// weights every piece into the n2 <= VX_SC_SEP_T2 coarse columns, and folds the threads' sums in a fixed order (shuffles, then the four waves through LDS):
+// the result is the same from run to run.
+#define VX_SC_SEP_T2 8
+#define VX_SC_SEP_U 4
+__device__ __forceinline__ float vx_tap_weight(int j, int n, int bw, int t) {        // weight of fine index j in coarse index t
+    int i0, i1; float lam;
+    vx_src_coord(j, n, bw, i0, i1, lam);
+    return (i0 == t ? 1.0f - lam : 0.0f) + (i1 == t ? lam : 0.0f);
+}
+// fine indices [lo, hi) that can touch coarse index t: ratio * j in (t - 1, t + 1), one more on either side for the rounding of ratio * j (a zero weight skips the row)
+__device__ __forceinline__ void vx_tap_range(int t, int n, int bw, int& lo, int& hi) {
+    if (n < 2) { lo = 0; hi = bw; return; }
+    lo = t > 0 ? ((t - 1) * (bw - 1)) / (n - 1) - 1 : 0;
+    hi = ((t + 1) * (bw - 1) + (n - 2)) / (n - 1) + 2;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > bw ? bw : hi;
+}
+template <int VW>
+__device__ __forceinline__ void vx_scatter_bwd_sep2_rows(float (&acc)[VX_SC_SEP_T2], const float* __restrict__ box, const float* __restrict__ A2,
+                                                         const float* __restrict__ Wt0, const float* __restrict__ Wt1, const VxPwaPlan& P,
+                                                         int n2, int bw2, int lo0, int hi0, int lo1, int hi1) {
+    const int q = bw2 / VW, nr1 = hi1 - lo1, items = (hi0 - lo0) * nr1 * q;      // < 2^22: the box fits LDS-sized limits (vx_scatter_bwd_kind)
+    const VxFd fq = vx_fd(q), fr1 = vx_fd(nr1);
+    for (int e0 = threadIdx.x; e0 < items; e0 += 256 * VX_SC_SEP_U) {          // VX_SC_SEP_U pieces per trip, their loads issued together: one piece per trip was a
+        float g[VX_SC_SEP_U][VW], w[VX_SC_SEP_U];                               // chain of 14 memory round trips at the 32^3 level's coarse scale
+        int j2[VX_SC_SEP_U];
+#pragma unroll
+        for (int k = 0; k < VX_SC_SEP_U; ++k) {
+            const int e = e0 + k * 256;
+            w[k] = 0.0f; j2[k] = 0;
+#pragma unroll
+            for (int u = 0; u < VW; ++u) g[k][u] = 0.0f;
+            if (e < items) {
+                int part, r1;
+                const int r0 = vx_fdivmod(vx_fdivmod(e, fq, part), fr1, r1);
+                const int j0 = lo0 + r0, j1 = lo1 + r1;
+                j2[k] = part * VW;
+                w[k] = Wt0[j0] * Wt1[j1];
+                if (w[k] != 0.0f) {
+                    const float* __restrict__ src = box + ((long)j0 * P.grid[1] + j1) * P.grid[2] + j2[k];
+                    if constexpr (VW == 4) { const float4 g4 = *reinterpret_cast<const float4*>(src); g[k][0] = g4.x; g[k][1] = g4.y; g[k][2] = g4.z; g[k][3] = g4.w; }
+                    else g[k][0] = src[0];
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < VX_SC_SEP_U; ++k) {
+            if (w[k] == 0.0f) continue;
+#pragma unroll
+            for (int t2 = 0; t2 < VX_SC_SEP_T2; ++t2)
+                if (t2 < n2) {
+                    const float* __restrict__ w2 = A2 + t2 * bw2 + j2[k];
+                    float s_ = 0.0f;
+#pragma unroll
+                    for (int u = 0; u < VW; ++u) s_ = fmaf(w2[u], g[k][u], s_);
+                    acc[t2] = fmaf(w[k], s_, acc[t2]);
+                }
+        }
+    }
+}
+__device__ __forceinline__ void vx_scatter_bwd_sep2_body(float* __restrict__ vx_sacc, const int X, const int Y, const int Z,
+                                                         const VxScPtrs& ptrs, float* __restrict__ dtok, const VxPwaPlan& P, int c, int m0, int M, int scale, int nx, int assign) {
+    int bx;
+    const int mm = vx_fdivmod(X, vx_fd(nx), bx);
+    const int m = m0 + mm;
+    const float* __restrict__ dout = ptrs.in[mm];
+    int a, cc, t1;
+    const int b = vx_fdivmod(Y, vx_fd(P.heads), a);
+    const int i = scale;
+    const int n0 = P.n[0], n1 = P.n[1], n2 = P.n[2];
+    const int t0 = vx_fdivmod(vx_fdivmod(Z, vx_fd(c), cc), vx_fd(n1), t1);
+    const int Nl = bx, N = P.woff[i] + Nl;
+    const int bw0 = n0 * P.small[i][0], bw1 = n1 * P.small[i][1], bw2 = n2 * P.small[i][2];
+    float* __restrict__ A2 = vx_sacc;                           // [n2][bw2]  weight of fine column j2 for coarse column t2
+    float* __restrict__ red = A2 + ((n2 * bw2 + 3) & ~3);       // [4 waves][VX_SC_SEP_T2]
+    float* __restrict__ Wt0 = red + 4 * VX_SC_SEP_T2;           // [bw0]  weight of fine plane j0 for this block's t0
+    float* __restrict__ Wt1 = Wt0 + bw0;                        // [bw1]  weight of fine row j1 for this block's t1
+    const VxFd fb2 = vx_fd(bw2);
+    for (int e = threadIdx.x; e < n2 * bw2; e += 256) {
+        int j;
+        const int t = vx_fdivmod(e, fb2, j);
+        A2[e] = vx_tap_weight(j, n2, bw2, t);
+    }
+    int lo0, hi0, lo1, hi1;
+    vx_tap_range(t0, n0, bw0, lo0, hi0);
+    vx_tap_range(t1, n1, bw1, lo1, hi1);
+    for (int j = lo0 + threadIdx.x; j < hi0; j += 256) Wt0[j] = vx_tap_weight(j, n0, bw0, t0);
+    for (int j = lo1 + threadIdx.x; j < hi1; j += 256) Wt1[j] = vx_tap_weight(j, n1, bw1, t1);
+    __syncthreads();
+    int W2, W1;
+    const int W0 = vx_fdivmod(vx_fdivmod(Nl, vx_fd(P.nwin[i][2]), W2), vx_fd(P.nwin[i][1]), W1);
+    const long V = (long)P.grid[0] * P.grid[1] * P.grid[2];
+    const float* __restrict__ box = dout + ((long)b * (P.nb * P.heads * c) + (long)(i * P.heads + a) * c + cc) * V
+                                  + ((long)(W0 * bw0) * P.grid[1] + W1 * bw1) * P.grid[2] + W2 * bw2;
+    float acc[VX_SC_SEP_T2];
+#pragma unroll
+    for (int t2 = 0; t2 < VX_SC_SEP_T2; ++t2) acc[t2] = 0.0f;
+    if (((bw2 | P.grid[2]) & 3) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0) vx_scatter_bwd_sep2_rows<4>(acc, box, A2, Wt0, Wt1, P, n2, bw2, lo0, hi0, lo1, hi1);
+    else vx_scatter_bwd_sep2_rows<1>(acc, box, A2, Wt0, Wt1, P, n2, bw2, lo0, hi0, lo1, hi1);
+#pragma unroll
+    for (int t2 = 0; t2 < VX_SC_SEP_T2; ++t2) {
+        for (int o = 32; o > 0; o >>= 1) acc[t2] += __shfl_xor(acc[t2], o, 64);
+        if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * VX_SC_SEP_T2 + t2] = acc[t2];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < n2) {
+        const int t2 = threadIdx.x;
+        const float v = (red[t2] + red[VX_SC_SEP_T2 + t2]) + (red[2 * VX_SC_SEP_T2 + t2] + red[3 * VX_SC_SEP_T2 + t2]);
+        float* __restrict__ dt = dtok + ((((long)b * P.heads + a) * P.Ntot + N) * ((long)M * P.l) + (long)m * P.l + ((t0 * n1 + t1) * n2 + t2)) * c + cc;
+        if (assign) *dt = v; else *dt += v;
+    }
+}
+
+// The whole adjoint of one level in ONE launch: block range [blk0, next blk0) belongs to one scale and runs that scale's body over its own (gx, gy, .) grid.  Every
+// element of dtok has one owning block and no block depends on another, so the ranges of the wide-cell scales come first (their blocks are the longest).
+struct VxScSeg { int blk0, kind, scale, gx, gy, nx, PT; };
+struct VxScMerged { int nseg; VxScSeg s[4]; };
+__global__ void __launch_bounds__(256) vx_pwa_scatter_bwd_merged_k(VxScPtrs ptrs, float* __restrict__ dtok, VxPwaPlan P, int c, int m0, int M, VxScMerged G, VxScZero z) {
+    extern __shared__ __attribute__((aligned(16))) float vx_sacc[];
+    const int id = blockIdx.x;
+    VxScSeg S = G.s[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (k < G.nseg && id >= G.s[k].blk0) S = G.s[k];
+    const unsigned r = (unsigned)(id - S.blk0);
+    const unsigned X = r % (unsigned)S.gx, yz = r / (unsigned)S.gx, Y = yz % (unsigned)S.gy, Z = yz / (unsigned)S.gy;
+    if (S.kind == 0) vx_scatter_bwd_ident_body(vx_sacc, X, Y, S.gx, S.gy, ptrs, dtok, P, c, m0, M, S.scale, S.nx, z);
+    else if (S.kind == 1) vx_scatter_bwd_gather_body(vx_sacc, X, Y, Z, ptrs, dtok, P, c, m0, M, S.scale, S.PT, S.nx, z.assign);
+    else vx_scatter_bwd_sep2_body(vx_sacc, X, Y, Z, ptrs, dtok, P, c, m0, M, S.scale, S.nx, z.assign);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1174,7 +1380,7 @@ static int vx_plan_check(const VxPwaPlan* P, const char* who) {
 }
 
 static int vx_gather_vec_enabled = 1;
-extern "C" int vx_pwa_gather_set_vec(int on) { vx_gather_vec_enabled = on ? 1 : 0; return 0; }      // A/B knob (tests): 0 = one lane per (cell / voxel, channel) in the gather and the scatter forward
+extern "C" int vx_pwa_gather_set_vec(int on) { vx_gather_vec_enabled = on == 2 ? 2 : (on ? 1 : 0); return 0; }      // A/B knob (tests): 0 = one lane per (cell / voxel, channel) in the gather and the scatter forward; 2 = the gather backward takes four voxels per thread at any size
 extern "C" int vx_pwa_gather_fwd(const float* src, float* tok, const VxPwaPlan* plan, int c, int m, int M, int B, void* stream) {
     if (int e = vx_plan_check(plan, "vx_pwa_gather_fwd")) return e;
     VX_REQUIRE(src && tok && c > 0 && m >= 0 && m < M && B > 0, "vx_pwa_gather_fwd: bad args");
@@ -1227,6 +1433,18 @@ extern "C" int vx_pwa_gather_all_bwd(const float* dtq, const float* dtk, const f
     if (cq % 4 == 0 && cv % 4 == 0 && vx_gather_vec_enabled) {
         const int CH = (cq % 8 == 0 && cv % 8 == 0) ? 8 : 4;
         const int nchm = (cq > cv ? cq : cv) / CH;
+        // four voxels of a row per thread, 16-byte stores: where that still leaves half the chip's wave slots filled (256 CUs x 32 waves).  Below, the launch waits for
+        // latencies rather than for its stores, and the one-voxel kernel's four times as many waves hide them better (16^3 grid, 8 channels per lane: 6.7 -> 7.7 us in the step)
+        const long waves4 = vx_cdiv(V / 4, 64) * (long)M * 3 * plan->nb * plan->heads * nchm * B;
+        bool rows4 = plan->grid[2] % 4 == 0 && (waves4 >= 4096 || vx_gather_vec_enabled == 2);
+        for (int k = 0; k < 3 * M; ++k) rows4 = rows4 && (reinterpret_cast<uintptr_t>(dsrcs[k]) & 15) == 0;
+        if (rows4) {
+            const dim3 g4(vx_cdiv(V / 4, 256), M * 3 * plan->nb * plan->heads * nchm, B);
+            if (CH == 8) hipLaunchKernelGGL(vx_pwa_gather_all_bwd_v4_k<8>, g4, dim3(256), 0, (hipStream_t)stream, ptrs, dtq, dtk, dtv, iq, ik, iv, *plan, cq, cv, M);
+            else hipLaunchKernelGGL(vx_pwa_gather_all_bwd_v4_k<4>, g4, dim3(256), 0, (hipStream_t)stream, ptrs, dtq, dtk, dtv, iq, ik, iv, *plan, cq, cv, M);
+            VX_LAUNCH_CHECK("vx_pwa_gather_all_bwd");
+            return 0;
+        }
         const dim3 g(vx_cdiv(V, 256), M * 3 * plan->nb * plan->heads * nchm, B);
         if (CH == 8) hipLaunchKernelGGL(vx_pwa_gather_all_bwd_v_k<8>, g, dim3(256), 0, (hipStream_t)stream, ptrs, dtq, dtk, dtv, iq, ik, iv, *plan, cq, cv, M);
         else hipLaunchKernelGGL(vx_pwa_gather_all_bwd_v_k<4>, g, dim3(256), 0, (hipStream_t)stream, ptrs, dtq, dtk, dtv, iq, ik, iv, *plan, cq, cv, M);
@@ -1281,6 +1499,60 @@ static int vx_scatter_bwd_kind(const VxPwaPlan* plan, int c, int B, int i) {
     const size_t shm3 = sizeof(float) * ((size_t)bw1 * bw2 + (size_t)bw1 * plan->n[2] + (size_t)plane_l(plan) + (size_t)plan->n[2] * bw2 + (size_t)plan->n[1] * bw1);
     if (vx_scatter_ident_enabled && shm3 <= 60 * 1024 && (long)B * plan->heads * c <= 65535) return 2;
     return 3;
+}
+// One launch for every scale (vx_pwa_scatter_bwd_merged_k) where each scale is of kind 0, 1 or 2; returns 1 and launches nothing otherwise (the caller takes the
+// per-scale launches below).  The separable scales run the sole-owner body, so with writes_all nothing has to be zeroed but the extra buffer.
+static int vx_scatter_merged_enabled = 1;
+extern "C" int vx_pwa_scatter_set_merged(int on) { vx_scatter_merged_enabled = on == 2 ? 2 : (on ? 1 : 0); return 0; }      // A/B knob (tests, probes): 0 = one launch per scale, 2 = one launch at any size
+static int vx_scatter_bwd_merged(const VxScPtrs& ptrs, float* dtok, const VxPwaPlan* plan, int c, int mcount, int M, int B, void* stream, bool writes_all,
+                                 float* extra_zero, long extra_floats) {
+    if (!vx_scatter_merged_enabled || plan->nb > 4) return 1;
+    // Taken by default where it was measured to win: B * M >= 8 volumes per call (three workloads at B = 4, M = 2: -0.5 .. -0.9 % of the step).  With B = 2, M = 1 the step
+    // was 1 % SLOWER with it (brats128, three alternating runs): the per-scale separable kernel sizes its plane chunks to the batch, the sole-owner body cannot.
+    if (vx_scatter_merged_enabled != 2 && (long)B * mcount < 8) return 1;
+    int kind[4];
+    bool has_ident = false;
+    for (int i = 0; i < plan->nb; ++i) {
+        kind[i] = vx_scatter_bwd_kind(plan, c, B, i);
+        const long nv = (long)plan->n[0] * plan->small[i][0] * plan->n[1] * plan->small[i][1] * plan->n[2] * plan->small[i][2];
+        if (kind[i] > 2 || (kind[i] == 2 && (plan->n[2] > VX_SC_SEP_T2 || nv >= (1 << 22)))) return 1;
+        has_ident = has_ident || kind[i] == 0;
+    }
+    if (extra_zero && !has_ident) return 1;            // (the identity blocks zero it)
+    VxScMerged G = {};
+    size_t shm = 0;
+    long blk = 0;
+    for (int want = 2; want >= 0; --want)
+        for (int i = plan->nb - 1; i >= 0; --i) {
+            if (kind[i] != want) continue;
+            VxScSeg& S = G.s[G.nseg++];
+            const int nwin = plan->nwin[i][0] * plan->nwin[i][1] * plan->nwin[i][2];
+            S.blk0 = (int)blk; S.kind = want; S.scale = i; S.gx = nwin * mcount; S.gy = B * plan->heads; S.nx = nwin; S.PT = 1;
+            long gz = 1;
+            size_t need;
+            if (want == 0) need = sizeof(float) * (size_t)plane_l(plan) * (c + 1);
+            else if (want == 1) {
+                const long nv = (long)plan->n[0] * plan->small[i][0] * plan->n[1] * plan->small[i][1] * plan->n[2] * plan->small[i][2];
+                const int nmax = plan->n[0] > plan->n[1] ? (plan->n[0] > plan->n[2] ? plan->n[0] : plan->n[2]) : (plan->n[1] > plan->n[2] ? plan->n[1] : plan->n[2]);
+                need = sizeof(float) * (((size_t)nv + 3) / 4 * 4 + (size_t)3 * nmax * VX_SC_TAPS * 2 + 3 * nmax);
+                int PT = 256 / plan->l;
+                S.PT = PT >= 4 ? 4 : (PT >= 2 ? 2 : 1);
+                gz = c;
+            } else {
+                need = sizeof(float) * ((((size_t)plan->n[2] * plan->n[2] * plan->small[i][2] + 3) & ~(size_t)3) + 4 * VX_SC_SEP_T2 + (size_t)plan->n[0] * plan->small[i][0] + (size_t)plan->n[1] * plan->small[i][1]);
+                gz = (long)c * plan->n[0] * plan->n[1];
+            }
+            shm = need > shm ? need : shm;
+            blk += (long)S.gx * S.gy * gz;
+        }
+    VX_REQUIRE(shm <= 128 * 1024, "vx_pwa_scatter_bwd: window (%d tokens x %d) does not fit LDS", plan->l, c);
+    if (blk >= (1L << 31)) return 1;
+    VxScZero z = {};
+    z.assign = writes_all ? 1 : 0;
+    z.extra = extra_zero; z.extra_n4 = extra_zero ? extra_floats / 4 : 0;
+    hipLaunchKernelGGL(vx_pwa_scatter_bwd_merged_k, dim3((unsigned)blk), dim3(256), shm, (hipStream_t)stream, ptrs, dtok, *plan, c, 0, M, G, z);
+    VX_LAUNCH_CHECK("vx_pwa_scatter_bwd");
+    return 0;
 }
 // writes_all: the caller did NOT zero dtok (needs every modality in this call and scale 0 on the identity kernel -- checked by the entry)
 static int vx_scatter_bwd_launch(const VxScPtrs& ptrs, float* dtok, const VxPwaPlan* plan, int c, int m0, int mcount, int M, int B, void* stream, bool writes_all = false,
@@ -1358,6 +1630,7 @@ extern "C" int vx_pwa_scatter_bwd_all_wz(const float* const* douts, float* dtok,
     for (int i = 1; i < plan->nb; ++i) if (vx_scatter_bwd_kind(plan, c, B, i) == 0) return 1;      // (a second identity scale would zero nothing but is not expected: keep the old path)
     VxScPtrs ptrs = {};
     for (int m = 0; m < M; ++m) { VX_REQUIRE(douts[m], "vx_pwa_scatter_bwd_all_w: null gradient %d", m); ptrs.in[m] = douts[m]; }
+    if (const int e = vx_scatter_bwd_merged(ptrs, dtok, plan, c, M, M, B, stream, true, extra_zero, extra_floats); e != 1) return e;
     return vx_scatter_bwd_launch(ptrs, dtok, plan, c, 0, M, M, B, stream, true, extra_zero, extra_floats);
 }
 // every modality in one launch per scale (douts[m] may not be NULL; dtok zeroed by the caller)
@@ -1366,6 +1639,7 @@ extern "C" int vx_pwa_scatter_bwd_all(const float* const* douts, float* dtok, co
     VX_REQUIRE(douts && dtok && c > 0 && M >= 1 && M <= 4 && B > 0, "vx_pwa_scatter_bwd_all: bad args");
     VxScPtrs ptrs = {};
     for (int m = 0; m < M; ++m) { VX_REQUIRE(douts[m], "vx_pwa_scatter_bwd_all: null gradient %d", m); ptrs.in[m] = douts[m]; }
+    if (const int e = vx_scatter_bwd_merged(ptrs, dtok, plan, c, M, M, B, stream, false, nullptr, 0); e != 1) return e;
     return vx_scatter_bwd_launch(ptrs, dtok, plan, c, 0, M, M, B, stream);
 }
 
