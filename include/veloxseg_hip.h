@@ -524,6 +524,23 @@ int vx_sw_accumulate(const float* win, float* acc, int C, int D, int H, int W, i
  * (-0.0 == +0.0).  C <= 256. */
 int vx_sw_finalize(const float* acc, float* out, unsigned char* labels, const float* cz, const float* cy, const float* cx,
                    int C, int D, int H, int W, void* stream);
+/* ---- mirror test-time augmentation of the sliding window (utils/inference_runtime.py, mirror_axes) ----
+ * A mirror is a mask 0..7: bit a set = spatial axis a (0 = D, 1 = H, 2 = W) is mirrored INSIDE the window, m_a(i) = r_a - 1 - i; otherwise m_a(i) = i.
+ * Every entry checks its arguments before it launches anything (mask outside 0..7, a window that leaves the volume, a window count outside the table,
+ * null pointers: -1).  Four voxels along x per thread where rw, W and the origins' x0 are multiples of 4 and the bases 16-byte aligned; scalar otherwise. */
+#define VX_SW_MAX_WINDOWS 16
+/* win[w, c, z, y, x] = vol[b_w, c, z0_w + m_z(z), y0_w + m_y(y), x0_w + m_x(x)] for the nwin <= VX_SW_MAX_WINDOWS windows of a window batch in ONE launch.
+ * vol: the whole (B, C, D, H, W) input; win: (nwin, C, rd, rh, rw).  table: HOST pointer to nwin x {b, z0, y0, x0} ints, read during the call and handed to
+ * the kernel by value (nothing is copied to the device, the caller may reuse the table at once). */
+int vx_sw_extract_mirror(const float* vol, float* win, const int* table, int nwin, int mask, int B, int C, int D, int H, int W, int rd, int rh, int rw, void* stream);
+/* wsum[r, z, y, x] (= when first, += otherwise) pred[r, m_z(z), m_y(y), m_x(x)] over r < rows = windows x classes: the mirrored prediction mirrored back and
+ * added to the window-local sum, one IEEE fp32 add per element.  pred and wsum must not alias. */
+int vx_sw_mirror_sum(const float* pred, float* wsum, long rows, int rd, int rh, int rw, int mask, int first, void* stream);
+/* acc[:, window] += weight * (wsum + mirrored-back pred) for ONE window (pred, wsum: (C, rd, rh, rw); acc: (C, D, H, W)): the last mirror's add fused into the
+ * blending.  Per element the sum, the product and the accumulation are rounded one after the other (no fma), so the result is that of vx_sw_mirror_sum followed
+ * by vx_sw_accumulate.  One call per window, in the reference's window order. */
+int vx_sw_mirror_accumulate(const float* pred, const float* wsum, float* acc, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0,
+                            int mask, float weight, void* stream);
 /* labels[b, v] = argmax_c logits[b, c, v] (first maximum, uint8): `outputs[0].argmax(dim=1)` of utils/metric/metrics.py:16 */
 int vx_argmax_channels(const float* logits, unsigned char* labels, int B, int C, long V, void* stream);
 /* conf[b, g, p] += #voxels with ground truth g and prediction p (uint64, NC*NC per sample; caller zeroes it): the sufficient statistic of

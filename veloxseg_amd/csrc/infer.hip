@@ -3,6 +3,7 @@
 // (argmax + Dice), utils/metric/metrics.py:44-91 (metrics_tensor), utils/metric/metrics_brats.py:22-35 (Dice / cal_dice).
 // All kernels are HBM-bound streaming passes: float4 rows where the window geometry allows, one pass over the volume each.
 #include "vx_common.h"
+#include "../../include/veloxseg_hip.h"
 
 struct VxWin {
     int C, D, H, W;        // volume (one batch item): (C, D, H, W)
@@ -56,6 +57,84 @@ __global__ void __launch_bounds__(256) vx_sw_finalize_k(const float* acc, float*
             if (q > best || (q != q && !(best != best))) { best = q; arg = c; }    // NaN ranks highest, first occurrence wins (aten)
         }
         if (labels) labels[v] = (unsigned char)arg;
+    }
+}
+
+// ---- mirror test-time augmentation: the window movers (utils/inference_runtime.py, mirror_axes) -----------------------------------------------
+// A mirror is a mask: bit a set = spatial axis a (0 = D, 1 = H, 2 = W) runs backwards inside the window, m_a(i) = r_a - 1 - i.  All three kernels are
+// streaming passes indexed by their OUTPUT element, so stores are contiguous; a mirrored axis only changes where the rows (D, H) or the 16-byte groups of a row (W)
+// are read from: the lanes of a wave still read one contiguous stretch of every row, backwards for W, and a W-mirrored group of four is the 16-byte load at the
+// mirrored position with its lanes reversed.  V = 4: four voxels along x per thread (rw, W and every x0 multiples of 4, bases 16-byte aligned); V = 1 otherwise.
+struct VxWinTab { int b[VX_SW_MAX_WINDOWS], z0[VX_SW_MAX_WINDOWS], y0[VX_SW_MAX_WINDOWS], x0[VX_SW_MAX_WINDOWS]; };       // batch item and origin of every window of a launch, by value
+
+__device__ __forceinline__ float4 vx_rev4(float4 v, bool on) { return on ? make_float4(v.w, v.z, v.y, v.x) : v; }
+
+// win[w, c, z, y, x] = vol[b_w, c, z0_w + m_z(z), y0_w + m_y(y), x0_w + m_x(x)];  blockIdx.y = w (the table is read with scalar loads)
+template <int V>
+__global__ void __launch_bounds__(256) vx_sw_extract_mirror_k(const float* __restrict__ vol, float* __restrict__ win, VxWin P, VxWinTab T, int mask) {
+    const int w = blockIdx.y;
+    const int rwv = P.rw / V;
+    const long n = (long)P.C * P.rd * P.rh * rwv;
+    const float* __restrict__ src = vol + ((((long)T.b[w] * P.C) * P.D + T.z0[w]) * P.H + T.y0[w]) * P.W + T.x0[w];
+    float* __restrict__ dst = win + (long)w * n * V;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int xg = (int)(i % rwv);
+        long t = i / rwv;
+        const int y = (int)(t % P.rh); t /= P.rh;
+        const int z = (int)(t % P.rd);
+        const int c = (int)(t / P.rd);
+        const int zs = (mask & 1) ? P.rd - 1 - z : z, ys = (mask & 2) ? P.rh - 1 - y : y, xs = (mask & 4) ? P.rw - V - xg * V : xg * V;
+        const long s = (((long)c * P.D + zs) * P.H + ys) * P.W + xs;
+        if (V == 4) vx_st4(dst, i * 4, vx_rev4(vx_ld4(src, s), mask & 4));
+        else dst[i] = src[s];
+    }
+}
+
+// wsum[r, z, y, x] (= | +=) pred[r, m_z(z), m_y(y), m_x(x)] over r < rows (= windows * classes)
+template <int V>
+__global__ void __launch_bounds__(256) vx_sw_mirror_sum_k(const float* __restrict__ pred, float* __restrict__ wsum, long rows, int rd, int rh, int rw, int mask, int first) {
+    const int rwv = rw / V;
+    const long n = rows * rd * rh * rwv;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int xg = (int)(i % rwv);
+        long t = i / rwv;
+        const int y = (int)(t % rh); t /= rh;
+        const int z = (int)(t % rd);
+        const long r = t / rd;
+        const int zs = (mask & 1) ? rd - 1 - z : z, ys = (mask & 2) ? rh - 1 - y : y, xs = (mask & 4) ? rw - V - xg * V : xg * V;
+        const long s = ((r * rd + zs) * rh + ys) * rw + xs;
+        if (V == 4) {
+            float4 v = vx_rev4(vx_ld4(pred, s), mask & 4);
+            if (!first) { const float4 o = vx_ld4(wsum, i * 4); v = make_float4(__fadd_rn(o.x, v.x), __fadd_rn(o.y, v.y), __fadd_rn(o.z, v.z), __fadd_rn(o.w, v.w)); }
+            vx_st4(wsum, i * 4, v);
+        } else {
+            wsum[i] = first ? pred[s] : __fadd_rn(wsum[i], pred[s]);
+        }
+    }
+}
+
+// acc[c, z0+z, y0+y, x0+x] += weight * (wsum[c, z, y, x] + pred[c, m_z(z), m_y(y), m_x(x)]): the last mirror's add of one window fused into its blending (one launch per
+// window, in window order, like vx_sw_accumulate_k).  Three roundings per element, in this order: the sum, the product, the accumulation (no contraction).
+template <int V>
+__global__ void __launch_bounds__(256) vx_sw_mirror_accumulate_k(const float* __restrict__ pred, const float* __restrict__ wsum, float* __restrict__ acc, VxWin P, int mask, float weight) {
+    const int rwv = P.rw / V;
+    const long n = (long)P.C * P.rd * P.rh * rwv;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int xg = (int)(i % rwv);
+        long t = i / rwv;
+        const int y = (int)(t % P.rh); t /= P.rh;
+        const int z = (int)(t % P.rd);
+        const int c = (int)(t / P.rd);
+        const int zs = (mask & 1) ? P.rd - 1 - z : z, ys = (mask & 2) ? P.rh - 1 - y : y, xs = (mask & 4) ? P.rw - V - xg * V : xg * V;
+        const long s = (((long)c * P.rd + zs) * P.rh + ys) * P.rw + xs;
+        const long a = (((long)c * P.D + P.z0 + z) * P.H + P.y0 + y) * P.W + P.x0 + xg * V;
+        if (V == 4) {
+            const float4 v = vx_rev4(vx_ld4(pred, s), mask & 4), o = vx_ld4(wsum, i * 4), q = vx_ld4(acc, a);
+            vx_st4(acc, a, make_float4(__fadd_rn(q.x, __fmul_rn(weight, __fadd_rn(o.x, v.x))), __fadd_rn(q.y, __fmul_rn(weight, __fadd_rn(o.y, v.y))),
+                                       __fadd_rn(q.z, __fmul_rn(weight, __fadd_rn(o.z, v.z))), __fadd_rn(q.w, __fmul_rn(weight, __fadd_rn(o.w, v.w)))));
+        } else {
+            acc[a] = __fadd_rn(acc[a], __fmul_rn(weight, __fadd_rn(wsum[i], pred[s])));
+        }
     }
 }
 
@@ -126,6 +205,57 @@ extern "C" int vx_sw_finalize(const float* acc, float* out, unsigned char* label
     VX_REQUIRE(C > 0 && C <= 256 && D > 0 && H > 0 && W > 0, "vx_sw_finalize: bad shape");
     vx_sw_finalize_k<<<dim3(vx_grid_for((long)D * H * W)), dim3(256), 0, (hipStream_t)stream>>>(acc, out, labels, cz, cy, cx, C, D, H, W);
     VX_LAUNCH_CHECK("vx_sw_finalize");
+    return 0;
+}
+
+static inline bool vx_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// grid of a streaming pass over n work items (guide: ~8 blocks per CU, the rest by the grid-stride loop)
+static inline int vx_stream_grid(long n, int rows = 1) { long g = (n + 255) / 256, cap = 2048 / rows; if (cap < 1) cap = 1; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
+
+extern "C" int vx_sw_extract_mirror(const float* vol, float* win, const int* table, int nwin, int mask, int B, int C, int D, int H, int W, int rd, int rh, int rw, void* stream) {
+    VX_REQUIRE(mask >= 0 && mask <= 7, "vx_sw_extract_mirror: mirror mask %d outside 0..7", mask);
+    VX_REQUIRE(nwin >= 1 && nwin <= VX_SW_MAX_WINDOWS, "vx_sw_extract_mirror: %d windows, the table holds 1..%d", nwin, VX_SW_MAX_WINDOWS);
+    VX_REQUIRE(vol && win && table, "vx_sw_extract_mirror: null pointer");
+    VX_REQUIRE(B > 0, "vx_sw_extract_mirror: non-positive batch");
+    VxWinTab T{};
+    bool v4 = rw % 4 == 0 && W % 4 == 0 && vx_al16(vol) && vx_al16(win);
+    for (int k = 0; k < nwin; ++k) {
+        T.b[k] = table[4 * k]; T.z0[k] = table[4 * k + 1]; T.y0[k] = table[4 * k + 2]; T.x0[k] = table[4 * k + 3];
+        VX_REQUIRE(T.b[k] >= 0 && T.b[k] < B, "vx_sw_extract_mirror: window %d names batch item %d of %d", k, T.b[k], B);
+        VxWin Pk{C, D, H, W, rd, rh, rw, T.z0[k], T.y0[k], T.x0[k]};
+        if (int e = vx_win_check(Pk, "vx_sw_extract_mirror")) return e;
+        v4 = v4 && T.x0[k] % 4 == 0;
+    }
+    VxWin P{C, D, H, W, rd, rh, rw, 0, 0, 0};
+    const long n = (long)C * rd * rh * rw;
+    if (v4) vx_sw_extract_mirror_k<4><<<dim3(vx_stream_grid(n / 4, nwin), nwin), dim3(256), 0, (hipStream_t)stream>>>(vol, win, P, T, mask);
+    else vx_sw_extract_mirror_k<1><<<dim3(vx_stream_grid(n, nwin), nwin), dim3(256), 0, (hipStream_t)stream>>>(vol, win, P, T, mask);
+    VX_LAUNCH_CHECK("vx_sw_extract_mirror");
+    return 0;
+}
+
+extern "C" int vx_sw_mirror_sum(const float* pred, float* wsum, long rows, int rd, int rh, int rw, int mask, int first, void* stream) {
+    VX_REQUIRE(mask >= 0 && mask <= 7, "vx_sw_mirror_sum: mirror mask %d outside 0..7", mask);
+    VX_REQUIRE(rows > 0 && rd > 0 && rh > 0 && rw > 0, "vx_sw_mirror_sum: non-positive extent");
+    VX_REQUIRE(pred && wsum && pred != wsum, "vx_sw_mirror_sum: null or aliased pointer");
+    const long n = rows * rd * rh * rw;
+    if (rw % 4 == 0 && vx_al16(pred) && vx_al16(wsum)) vx_sw_mirror_sum_k<4><<<dim3(vx_stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(pred, wsum, rows, rd, rh, rw, mask, first);
+    else vx_sw_mirror_sum_k<1><<<dim3(vx_stream_grid(n)), dim3(256), 0, (hipStream_t)stream>>>(pred, wsum, rows, rd, rh, rw, mask, first);
+    VX_LAUNCH_CHECK("vx_sw_mirror_sum");
+    return 0;
+}
+
+extern "C" int vx_sw_mirror_accumulate(const float* pred, const float* wsum, float* acc, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0,
+                                       int mask, float weight, void* stream) {
+    VX_REQUIRE(mask >= 0 && mask <= 7, "vx_sw_mirror_accumulate: mirror mask %d outside 0..7", mask);
+    VxWin P{C, D, H, W, rd, rh, rw, z0, y0, x0};
+    if (int e = vx_win_check(P, "vx_sw_mirror_accumulate")) return e;
+    VX_REQUIRE(pred && wsum && acc, "vx_sw_mirror_accumulate: null pointer");
+    const long n = (long)C * rd * rh * rw;
+    if (rw % 4 == 0 && W % 4 == 0 && x0 % 4 == 0 && vx_al16(pred) && vx_al16(wsum) && vx_al16(acc))
+        vx_sw_mirror_accumulate_k<4><<<dim3(vx_stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(pred, wsum, acc, P, mask, weight);
+    else vx_sw_mirror_accumulate_k<1><<<dim3(vx_stream_grid(n)), dim3(256), 0, (hipStream_t)stream>>>(pred, wsum, acc, P, mask, weight);
+    VX_LAUNCH_CHECK("vx_sw_mirror_accumulate");
     return 0;
 }
 

@@ -7,6 +7,8 @@ HIP kernels (csrc/infer.hip), the predictor being the HIP VeloxSeg forward.  Sem
 """
 from __future__ import annotations
 
+import ctypes
+import itertools
 import math
 import os
 from typing import Callable, List, Optional, Sequence, Tuple
@@ -52,6 +54,67 @@ def _axis_counts(starts_axis: Sequence[int], r: int, m: int, device) -> torch.Te
     for s in starts_axis:
         c[s:s + r] += 1.0
     return c.to(device)
+
+
+SW_MAX_WINDOWS = 16  # VX_SW_MAX_WINDOWS of include/veloxseg_hip.h: windows per vx_sw_extract_mirror launch (a larger sw_batch_size takes several)
+
+
+def mirror_schedule(axes: Sequence[int]) -> List[int]:
+    """the mirrors of a test-time augmentation over the spatial axes `axes` (0 = D, 1 = H, 2 = W; any order), as masks (bit a = axis a mirrored) in nnU-Net's order:
+    the identity, then every itertools.combinations(sorted axes, i) for i = 1 .. len(axes).  (0, 1, 2) -> [0, 1, 2, 4, 3, 5, 6, 7]."""
+    axes = list(axes)
+    if any(isinstance(a, (bool, float, str)) or a not in (0, 1, 2) for a in axes):
+        raise ValueError(f"mirror_axes: spatial axes out of (0, 1, 2) expected, got {axes}")
+    axes = [int(a) for a in axes]
+    if len(set(axes)) != len(axes):
+        raise ValueError(f"mirror_axes: duplicate axis in {axes}")
+    axes = sorted(axes)
+    return [0] + [sum(1 << a for a in c) for i in range(1, len(axes) + 1) for c in itertools.combinations(axes, i)]
+
+
+def _extract_mirrored(inputs, win, idxs, starts, num_win, geom, mask, stream):
+    """win[k] = window idxs[k] of the (B, C, D, H, W) input, mirrored by `mask` inside its own extent: one launch per SW_MAX_WINDOWS windows"""
+    B, C, D, Hh, W, rd, rh, rw = geom
+    for g in range(0, len(idxs), SW_MAX_WINDOWS):
+        part = idxs[g:g + SW_MAX_WINDOWS]
+        tab = (ctypes.c_int * (4 * len(part)))(*[v for i in part for v in (i // num_win,) + tuple(starts[i % num_win])])
+        H.call("vx_sw_extract_mirror", H.P(inputs), H.P(win[g:g + len(part)]), ctypes.addressof(tab), len(part), mask, B, C, D, Hh, W, rd, rh, rw, stream)
+
+
+def _mirrored_forwards(inputs, win, idxs, starts, num_win, geom, masks, run, wsum, stream, span=None):
+    """the len(masks) forwards of ONE window batch, in schedule order, all on `stream`: -> (wsum, prediction of the last mask).  wsum holds
+    P(w) + sum of flip_f(P(flip_f(w))) over every mask but the last, added in schedule order; the last one is added by vx_sw_mirror_accumulate on its way into the
+    blending.  A taped predictor hands out its static output, which its next replay overwrites: every prediction is folded into wsum on the same stream before
+    the next forward is started.  wsum: a (sw_batch_size, K, rd, rh, rw) buffer from an earlier batch, or None (allocated here, on the current stream).
+    span = (j0, j1): only the schedule positions j0 .. j1 - 1 (-> (wsum, None) when the last mask is not among them)."""
+    rd, rh, rw = geom[5:]
+    prob = None
+    for j in range(*(span or (0, len(masks)))):
+        f = masks[j]
+        _extract_mirrored(inputs, win, idxs, starts, num_win, geom, f, stream)
+        prob = run(win)
+        if isinstance(prob, (list, tuple)):
+            prob = prob[0]
+        prob = prob.contiguous().float()
+        if tuple(prob.shape[2:]) != (rd, rh, rw) or prob.shape[0] != len(idxs):
+            raise NotImplementedError("predictor output must have the window's spatial size")
+        if wsum is None:
+            wsum = torch.empty_like(prob)
+        if tuple(wsum.shape[1:]) != tuple(prob.shape[1:]) or wsum.shape[0] < len(idxs):
+            raise NotImplementedError("predictor output changed its shape between the forwards of a volume")
+        if j == len(masks) - 1:
+            return wsum, prob
+        H.call("vx_sw_mirror_sum", H.P(prob), H.P(wsum[:len(idxs)]), len(idxs) * int(prob.shape[1]), rd, rh, rw, f, 1 if j == 0 else 0, stream)
+    return wsum, None
+
+
+def _accumulate_mirrored(prob, wsum, acc, idxs, starts, num_win, geom, mask, weight, stream):
+    """acc[window] += weight * (wsum + flip_mask(prob)), one launch per window in window order"""
+    D, Hh, W, rd, rh, rw = geom[2:]
+    K = int(prob.shape[1])
+    for k, i in enumerate(idxs):
+        z0, y0, x0 = starts[i % num_win]
+        H.call("vx_sw_mirror_accumulate", H.P(prob[k]), H.P(wsum[k]), H.P(acc[i // num_win]), K, D, Hh, W, rd, rh, rw, z0, y0, x0, mask, weight, stream)
 
 
 # two window batches in flight (round 6): each forward of a window batch is a ~250-launch tape that leaves most of the chip idle at the reference's sw_batch_size of 2; the next
@@ -118,14 +181,91 @@ def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi):
     return acc, K
 
 
+def _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks):
+    """_pipelined with mirror test-time augmentation: the len(masks) forwards of a window batch run one after the other on that batch's slot (its tape replica, its
+    stream); two batches stay in flight, their forwards issued in turn, and the blending of batch i + 1 waits for the one of batch i, so the sums are those of the
+    sequential loop bit for bit."""
+    B, C, D, Hh, W, rd, rh, rw = geom
+    dev = inputs.device
+    cur = torch.cuda.current_stream(dev)
+    streams = _SW_STREAMS.setdefault(str(dev), [torch.cuda.Stream(device=dev) for _ in range(SW_INFLIGHT)])
+    wins = [torch.empty((swb, C, rd, rh, rw), device=dev, dtype=torch.float32) for _ in range(SW_INFLIGHT)]
+    weight = 1.0 / len(masks)
+    # the FIRST forward of the first batch the plain way, on the caller's stream (captures / validates the tape of this shape; tells us K).  Its other forwards are
+    # slot 0's: a first batch held on the caller's stream to its end would run its len(masks) forwards with nothing beside them
+    wsum0, _ = _mirrored_forwards(inputs, wins[0], list(range(swb)), starts, num_win, geom, masks, predictor, None, H.stream_ptr(), span=(0, 1))
+    K = int(wsum0.shape[1])
+    acc = torch.zeros((B, K, D, Hh, W), device=dev, dtype=torch.float32)
+    wsums = [torch.empty_like(wsum0) if s_ else wsum0 for s_ in range(SW_INFLIGHT)]
+    for s_ in streams:
+        s_.wait_stream(cur)
+    last_acc = None
+
+    def run(w, slot):
+        out = predictor.forward_slot(w, 1 + slot)
+        if out is None:                                      # no replica (capture refused): the eager launches, on this stream
+            out = predictor.model(w) if hasattr(predictor, "model") else predictor(w)
+        return out
+    nb = total // swb
+    idxs_of = lambda bi: list(range(bi * swb, (bi + 1) * swb))
+    for b0 in range(0, nb, SW_INFLIGHT):
+        # the batches in flight are enqueued forward by forward in turn (batch b0 mask 0, batch b0 + 1 mask 0, batch b0 mask 1, ...); enqueued batch by batch -- all
+        # len(masks) tapes of one, then those of the other -- the two hardly overlap (DESIGN.md section 21.3)
+        group = range(b0, min(b0 + SW_INFLIGHT, nb))
+        last = {}
+        for j in range(len(masks)):
+            for bi in group:
+                if bi == 0 and j == 0:
+                    continue                                 # (done above, on the caller's stream)
+                slot = bi % SW_INFLIGHT
+                with torch.cuda.stream(streams[slot]):
+                    _, prob = _mirrored_forwards(inputs, wins[slot], idxs_of(bi), starts, num_win, geom, masks, lambda w, s_=slot: run(w, s_), wsums[slot],
+                                                 streams[slot].cuda_stream, span=(j, j + 1))
+                last[bi] = prob
+        for bi in group:
+            st_ = streams[bi % SW_INFLIGHT]
+            with torch.cuda.stream(st_):
+                if last_acc is not None:
+                    st_.wait_event(last_acc)                 # blending in window order
+                _accumulate_mirrored(last[bi], wsums[bi % SW_INFLIGHT], acc, idxs_of(bi), starts, num_win, geom, masks[-1], weight, st_.cuda_stream)
+                last_acc = torch.cuda.Event()
+                last_acc.record(st_)
+    for s_ in streams:
+        cur.wait_stream(s_)
+    return acc, K
+
+
+def _run_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks):
+    """mirror test-time augmentation: len(masks) forwards per window batch, summed window by window -> (acc, K).  Pipelined under the plain driver's conditions
+    (a predictor with tape replicas, at least two full window batches, no ragged one), else one batch after the other on the caller's stream."""
+    if SW_PIPELINE and hasattr(predictor, "forward_slot") and total >= 2 * swb and total % swb == 0:
+        return _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks)
+    B, C, D, Hh, W, rd, rh, rw = geom
+    acc = win = wsum = None
+    for g in range(0, total, swb):
+        idxs = list(range(g, min(g + swb, total)))
+        if win is None:
+            win = torch.empty((len(idxs), C, rd, rh, rw), device=inputs.device, dtype=torch.float32)
+        wsum, prob = _mirrored_forwards(inputs, win[:len(idxs)], idxs, starts, num_win, geom, masks, predictor, wsum, H.stream_ptr())
+        if acc is None:
+            acc = torch.zeros((B, int(prob.shape[1]), D, Hh, W), device=inputs.device, dtype=torch.float32)
+        _accumulate_mirrored(prob, wsum, acc, idxs, starts, num_win, geom, masks[-1], 1.0 / len(masks), H.stream_ptr())
+    return acc, int(acc.shape[1])
+
+
 _SW_STREAMS = {}
 
 
 def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, predictor: Callable, overlap: float = 0.25,
                              mode: str = "constant", padding_mode: str = "constant", cval: float = 0.0, return_labels: bool = False,
-                             **unsupported):
+                             mirror_axes: Sequence[int] = (), sw_device=None, device=None, **unsupported):
     """-> blended predictions (B, K, D, H, W) fp32, or (predictions, uint8 argmax labels (B, 1, D, H, W)) with return_labels.
-    Only the arguments the reference drivers use are supported (constant blending / padding); anything else raises."""
+    Only the arguments the reference drivers use are supported (constant blending / padding); anything else raises.
+    mirror_axes: mirror test-time augmentation over these spatial axes (0 = D, 1 = H, 2 = W): every window is also predicted under each mirror of
+    mirror_schedule(mirror_axes), the predictions are mirrored back and summed window by window in schedule order, and the window enters the blending with weight
+    1 / n -- bit for bit the result of the plain call on the predictor that averages its mirrored predictions.  () = off.
+    sw_device: where the windows are predicted -- None or the inputs' device (there is no other path).  device: where the RESULT lives (the reference's huge-volume
+    call passes "cpu"); the blending itself stays on the GPU and the result is moved once at the end."""
     if str(mode).lower() not in ("constant", "blendmode.constant") or str(padding_mode).lower() not in ("constant", "pytorchpadmode.constant"):
         raise NotImplementedError("veloxseg_amd sliding window: constant blending / constant padding only (what utils/inference_*.py use)")
     if unsupported:
@@ -134,6 +274,13 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_b
         raise ValueError("sliding window expects (B, C, D, H, W)")
     if not inputs.is_cuda:
         raise RuntimeError("veloxseg_amd sliding window runs on MI355X only (no CPU path); move the volume to a cuda device")
+    if sw_device is not None:
+        swd = torch.device(sw_device)
+        if swd.type == "cuda" and swd.index is None:
+            swd = torch.device("cuda", torch.cuda.current_device())
+        if swd != inputs.device:
+            raise ValueError(f"veloxseg_amd sliding window: windows are predicted where the inputs are ({inputs.device}), not on sw_device={sw_device}")
+    masks = mirror_schedule(mirror_axes if mirror_axes is not None else ())
     inputs = inputs.contiguous().float()
     B, C = inputs.shape[:2]
     image_size_ = list(inputs.shape[2:])
@@ -159,6 +306,9 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_b
     total = num_win * B
     acc = None
     K = None
+    if len(masks) > 1:
+        acc, K = _run_mirrored(inputs, predictor, starts, num_win, total, sw_batch_size, (B, C, D, Hh, W, rd, rh, rw), masks)
+        total = 0                                           # (the plain path below has nothing left)
     if (SW_PIPELINE and hasattr(predictor, "forward_slot") and total >= 2 * sw_batch_size and total % sw_batch_size == 0):
         done = _pipelined(inputs, predictor, starts, num_win, total, sw_batch_size, (C, D, Hh, W), (rd, rh, rw))
         if done is not None:
@@ -191,11 +341,17 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_b
         crop = (slice(None), slice(None)) + tuple(slice(l, l + m) for l, m in zip(lo, image_size_))
         acc = acc[crop]
         labels = labels[crop].contiguous() if return_labels else None
+    if device is not None:
+        acc = acc.to(device)
+        labels = labels.to(device) if return_labels else None
     return (acc, labels) if return_labels else acc
 
 
 def sliding_window_predict(inputs, predictor, roi_size, sw_batch_size, test_config, **kwargs):
-    """reference signature (utils/inference_runtime.py:4-19): overlap comes from test_config["sliding_window"]["overlap"]"""
+    """reference signature (utils/inference_runtime.py:4-19): overlap comes from test_config["sliding_window"]["overlap"], and so does mirror_axes
+    (test_config["sliding_window"]["mirror_axes"], optional) unless the keyword is given"""
+    if "mirror_axes" not in kwargs and test_config["sliding_window"].get("mirror_axes") is not None:
+        kwargs["mirror_axes"] = tuple(test_config["sliding_window"]["mirror_axes"])
     return sliding_window_inference(inputs, roi_size, sw_batch_size, predictor=predictor, overlap=test_config["sliding_window"]["overlap"], **kwargs)
 
 
@@ -212,7 +368,8 @@ class Net(torch.nn.Module):
 
 
 @torch.inference_mode()
-def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, overlap: float, taped: bool = True, postprocess=None):
+def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, overlap: float, taped: bool = True, postprocess=None,
+                 mirror_axes: Sequence[int] = ()):
     """eval-mode sliding-window segmentation of one (B, C, D, H, W) volume -> (blended logits, uint8 label map).
     postprocess (a utils.components.Postprocess, or the dict its from_config takes): the returned label map is the cleaned-up one (components below a voxel
     count dropped / the k largest kept, on the GPU); the returned logits are untouched.
@@ -220,7 +377,8 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
     is the eager forward's (checked at capture).  The accumulator of the blending reads the predictor's static output before the next replay
     overwrites it (same stream).  The predictor hangs on the model object (no process-wide cache, nothing outlives the model) and re-captures
     when the parameters / buffers were re-homed since the capture (TrainEngine's flat buffer, .to(), a parameter swap): a tape bakes in raw
-    device pointers."""
+    device pointers.
+    mirror_axes: mirror test-time augmentation (sliding_window_inference); mirrored windows have the window's shape and replay the same tape and replicas."""
     was_training = model.training
     model.eval()
     try:
@@ -233,7 +391,7 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
             if pred is None:
                 pred = TapedPredictor(net)
                 model.__dict__["_vx_taped_predictor"] = pred       # plain attribute (not a sub-module): dies with the model
-        logits, labels = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True)
+        logits, labels = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True, mirror_axes=mirror_axes)
         if postprocess is not None:
             from .components import Postprocess
             labels = (postprocess if isinstance(postprocess, Postprocess) else Postprocess.from_config(postprocess))(labels)
