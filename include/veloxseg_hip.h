@@ -509,9 +509,29 @@ int vx_upconv_k2s2_bwd_data(const float* dy, const float* w, float* dx, int B, i
 int vx_upconv_k2s2_wgrad_ok(int Ci, int Co);
 int vx_upconv_k2s2_wgrad(const float* x, const float* dy, float* dw, int B, int Ci, int Co, int d, int h, int wd, void* stream);
 
-/* fused AdamW on flat buffers (torch.optim.AdamW maths; config/train_config_bs4.json:66-72); g is scaled by grad_scale first */
+/* fused AdamW on flat buffers (torch.optim.AdamW maths; config/train_config_bs4.json:66-72); g is scaled by grad_scale first.
+ * Rounding: every element is updated with the same written-out fused multiply-adds (decay = fma(-lr, wd, 1), m = fma(b1, m, (1-b1) g), v = fma(b2, v, ((1-b2) g) g),
+ * p = fma(p, decay, -(lr/bc1) (m / denom))), whichever kernel reaches it.  For 16-byte aligned buffers and the first n - n % 4 elements these are the roundings this
+ * entry always had; the last n % 4 elements and unaligned buffers used to be left to the compiler's contraction (which fused nothing there) and can differ from
+ * earlier builds in the last bit. */
 int vx_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, long step, float grad_scale, void* stream);
+/* Global-norm gradient clipping, EMA weights and param groups inside the optimizer step (beyond the reference).
+ * vx_grad_sqnorm_partials: ws[0 .. vx_grad_sqnorm_blocks()) = per-workgroup shares of sum g^2, every square and sum in fp64, on a fixed grid in a fixed order (no atomics):
+ * bit-equal between runs and between ranks that hold the same gradient.  One call per gradient range, into disjoint slots of ws; alignment gaps of g must hold zeros. */
+int vx_grad_sqnorm_blocks(void);
+int vx_grad_sqnorm_partials(const float* g, long n, double* ws, void* stream);
+/* vx_adamw_step with three optional extras, all resolved on the device (no host synchronisation); with all of them off p, m, v are bit-identical to vx_adamw_step.
+ *  clip   ws != NULL: every workgroup adds the nws partials in one fixed order, total = sqrt(S) * grad_scale, coef = min(1, max_norm / (total + 1e-6)) in fp64
+ *         (torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False: a NaN norm gives NaN, an infinite one 0), rounded to fp32; the update sees (g * grad_scale) * coef.
+ *         max_norm <= 0: coef = 1 (the norm is still reported).  write_stats != 0: this call writes stats[0] = total, stats[1] = coef and adds 1 to stats[2] when total is
+ *         not finite (stats = 4 floats on the device; set write_stats in ONE of the range calls of a step).
+ *  EMA    ema != NULL: e = fmaf(one_minus_decay, p_new - e, e) after the parameter update.
+ *  groups chunk_group != NULL: device table, one group index per 64 elements of THIS call's range (pass table + lo / 64 for a range starting at lo, lo % 64 == 0);
+ *         group_lr / group_wd are HOST arrays of ngroups <= 8 values that replace lr / weight_decay; betas, eps and step are shared. */
+int vx_adamw_step_ex(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float weight_decay, long step,
+                     float grad_scale, const double* ws, int nws, float max_norm, float* stats, int write_stats, float* ema, float one_minus_decay,
+                     const unsigned char* chunk_group, const float* group_lr, const float* group_wd, int ngroups, void* stream);
 
 /* ---- sliding-window inference + label metrics -------------------------------------------------------
  * Replaces monai.inferers.sliding_window_inference as called from utils/inference_runtime.py:4-19 (constant blending) and the

@@ -562,18 +562,31 @@ __global__ void __launch_bounds__(256) vx_upsample_adj_axis_k(const float* __res
 // ---------------------------------------------------------------------------------------------
 // fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics, amsgrad=False, maximize=False)
 // ---------------------------------------------------------------------------------------------
+// the update of ONE element, shared by every AdamW kernel below (gi = the gradient as the update sees it: scaled, clipped); p, m, v are updated in place.
+//   p <- p (1 - lr wd) - (lr / bc1) m / (sqrt(v) / bc2_sqrt + eps),   m <- b1 m + (1 - b1) g,   v <- b2 v + (1 - b2) g g
+// Which products are fused into an addition is WRITTEN here and the compiler is kept from choosing (contract(off)): left to it, the four-element and the one-element
+// kernel of vx_adamw_step fused different products, and two kernels of one formula differed in the last bit.  The fusions are those of the four-element kernel, the
+// one every 16-byte aligned buffer -- every range of the engine's flat buffers -- goes through, so its results are unchanged to the bit.
+__device__ __forceinline__ void vx_adamw_elem(float gi, float& p, float& m, float& v, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    const float decay = fmaf(-lr, wd, 1.0f);
+    const float mi = fmaf(b1, m, (1.0f - b1) * gi);
+    const float vi = fmaf(b2, v, ((1.0f - b2) * gi) * gi);
+    m = mi;
+    v = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p = fmaf(p, decay, -((lr / bc1) * (mi / denom)));
+}
+
 __global__ void __launch_bounds__(256) vx_adamw_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                   long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    vx_adamw_elem(g[i] * gscale, pi, mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - (lr / bc1) * (mi / denom);
+    p[i] = pi;
 }
 
 // the same update on four consecutive elements per thread (16-byte accesses; the arithmetic of an element is unchanged: IEEE division and square root as torch.optim.AdamW)
@@ -586,17 +599,112 @@ __global__ void __launch_bounds__(256) vx_adamw4_k(float4* __restrict__ p, const
     float po[4], mo[4], vo[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float gi = gv[k] * gscale;
-        const float pi = pv[k] * (1.0f - lr * wd);
-        const float mi = b1 * mv[k] + (1.0f - b1) * gi;
-        const float vi = b2 * vv[k] + (1.0f - b2) * gi * gi;
-        mo[k] = mi; vo[k] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        po[k] = pi - (lr / bc1) * (mi / denom);
+        po[k] = pv[k]; mo[k] = mv[k]; vo[k] = vv[k];
+        vx_adamw_elem(gv[k] * gscale, po[k], mo[k], vo[k], lr, b1, b2, eps, wd, bc1, bc2_sqrt);
     }
     m[i] = make_float4(mo[0], mo[1], mo[2], mo[3]);
     v[i] = make_float4(vo[0], vo[1], vo[2], vo[3]);
     p[i] = make_float4(po[0], po[1], po[2], po[3]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the optimizer step with global-norm clipping, EMA weights and param groups (vx_adamw_step_ex)
+// ---------------------------------------------------------------------------------------------
+#define VX_GN_BLOCKS 256          // partials per vx_grad_sqnorm_partials call: a fixed grid, so the summation order is a function of n (and of g's 16-byte alignment) alone
+#define VX_ADAMW_MAX_GROUPS 8
+struct VxAdamwGroups { float lr[VX_ADAMW_MAX_GROUPS]; float wd[VX_ADAMW_MAX_GROUPS]; };
+
+// ws[blockIdx.x] = this block's share of sum g^2: squares and sums in fp64 (1e-20 .. 1e18 neither underflow nor overflow), thread t of the grid takes the 16-byte
+// groups t, t + T, ... in order, then the scalar tail the same way; wave butterfly, then waves 0..3 in order.  No atomics, nothing waits on another block: the same
+// gradient gives the same bits on every run and on every rank.
+__global__ void __launch_bounds__(256) vx_grad_sqnorm_k(const float* __restrict__ g, long n, double* __restrict__ ws) {
+    __shared__ double sm[4];
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nth = (long)gridDim.x * 256;
+    double q = 0.0;
+    long done = 0;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        const long n4 = n >> 2;
+        for (long i = tid; i < n4; i += nth) {
+            const float4 v4 = vx_ld4(g, 4 * i);
+            const double a = (double)v4.x, b = (double)v4.y, c = (double)v4.z, d = (double)v4.w;
+            q += a * a; q += b * b; q += c * c; q += d * d;
+        }
+        done = n4 << 2;
+    }
+    for (long i = done + tid; i < n; i += nth) { const double a = (double)g[i]; q += a * a; }
+    q = vx_wave_sum(q);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = q;
+    __syncthreads();
+    if (threadIdx.x == 0) ws[blockIdx.x] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+}
+
+// clip_grad_norm_'s coefficient from the partials, formed by every wave for itself: lane l adds ws[l], ws[l + 64], ... in order, then the wave butterfly (every lane of
+// every wave of every launch ends with the same bits: the adds of a butterfly step are commutative pairs).  total = ||g * gscale||, coef = min(1, max_norm / (total + 1e-6))
+// in fp64, rounded to fp32 once; a NaN norm gives a NaN coefficient and an infinite one 0, as torch.clamp(max=1) does (error_if_nonfinite=False).  All 64 lanes must call.
+__device__ __forceinline__ float vx_clip_coef(const double* __restrict__ ws, int nws, float max_norm, float gscale, double& total) {
+    double s = 0.0;
+    for (int j = threadIdx.x & 63; j < nws; j += 64) s += ws[j];
+    s = vx_wave_sum(s);
+    total = sqrt(s) * (double)gscale;
+    if (!(max_norm > 0.0f)) return 1.0f;
+    const double r = (double)max_norm / (total + 1e-6);
+    return (float)(r > 1.0 ? 1.0 : r);
+}
+
+// VEC: one thread = 4 consecutive elements (16-byte accesses), n counts float4s; else one element, `base` = index of element 0 of this launch in the range (chunk table)
+template <bool VEC>
+__global__ void __launch_bounds__(256) vx_adamw_ex_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
+                                                     long n, long base, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale,
+                                                     const double* __restrict__ ws, int nws, float max_norm, float* __restrict__ stats, float one_minus_decay,
+                                                     const unsigned char* __restrict__ chunk_group, VxAdamwGroups grp) {
+    const bool clip = ws != nullptr;
+    float coef = 1.0f;
+    if (clip) {
+        double total;
+        coef = vx_clip_coef(ws, nws, max_norm, gscale, total);
+        if (stats && blockIdx.x == 0 && threadIdx.x == 0) {          // (the launcher hands `stats` to ONE launch of a step: a plain read-modify-write is enough)
+            stats[0] = (float)total;
+            stats[1] = coef;
+            if (!(fabs(total) <= 1.79769313486231570815e308)) stats[2] += 1.0f;
+        }
+    }
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long e0 = VEC ? 4 * i : base + i;
+    if (chunk_group) {                   // a 64-element chunk never spans two parameters (and 4 | 64: never inside one thread's four elements)
+        const int gi = chunk_group[e0 >> 6];
+#pragma unroll
+        for (int k = 0; k < VX_ADAMW_MAX_GROUPS; ++k)
+            if (gi == k) { lr = grp.lr[k]; wd = grp.wd[k]; }
+    }
+    if (VEC) {
+        const float4 g4 = vx_ld4(g, e0), p4 = vx_ld4(p, e0), m4 = vx_ld4(m, e0), v4 = vx_ld4(v, e0);
+        const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
+        float po[4] = {p4.x, p4.y, p4.z, p4.w}, mo[4] = {m4.x, m4.y, m4.z, m4.w}, vo[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float gi = gv[k] * gscale;
+            if (clip) gi *= coef;
+            vx_adamw_elem(gi, po[k], mo[k], vo[k], lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        }
+        vx_st4(m, e0, make_float4(mo[0], mo[1], mo[2], mo[3]));
+        vx_st4(v, e0, make_float4(vo[0], vo[1], vo[2], vo[3]));
+        vx_st4(p, e0, make_float4(po[0], po[1], po[2], po[3]));
+        if (ema) {
+            const float4 e4 = vx_ld4(ema, e0);
+            vx_st4(ema, e0, make_float4(fmaf(one_minus_decay, po[0] - e4.x, e4.x), fmaf(one_minus_decay, po[1] - e4.y, e4.y),
+                                        fmaf(one_minus_decay, po[2] - e4.z, e4.z), fmaf(one_minus_decay, po[3] - e4.w, e4.w)));
+        }
+    } else {
+        float gi = g[i] * gscale;
+        if (clip) gi *= coef;
+        float pi = p[i], mi = m[i], vi = v[i];
+        vx_adamw_elem(gi, pi, mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+        if (ema) { const float e = ema[i]; ema[i] = fmaf(one_minus_decay, pi - e, e); }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -847,6 +955,47 @@ extern "C" int vx_adamw_step(float* p, const float* g, float* m, float* v, long 
         hipLaunchKernelGGL(vx_adamw_k, dim3(vx_cdiv(n - 4 * n4, 256)), dim3(256), 0, (hipStream_t)stream, p + 4 * n4, g + 4 * n4, m + 4 * n4, v + 4 * n4, n - 4 * n4, lr, beta1, beta2, eps,
                            weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
     VX_LAUNCH_CHECK("vx_adamw_step");
+    return 0;
+}
+
+extern "C" int vx_grad_sqnorm_blocks(void) { return VX_GN_BLOCKS; }
+
+extern "C" int vx_grad_sqnorm_partials(const float* g, long n, double* ws, void* stream) {
+    VX_REQUIRE(g && ws && n > 0, "vx_grad_sqnorm_partials: bad args (null pointer or n <= 0)");
+    // always every block: each one writes its partial (0 when it has no element), so the workspace needs no zero-fill
+    hipLaunchKernelGGL(vx_grad_sqnorm_k, dim3(VX_GN_BLOCKS), dim3(256), 0, (hipStream_t)stream, g, n, ws);
+    VX_LAUNCH_CHECK("vx_grad_sqnorm_partials");
+    return 0;
+}
+
+extern "C" int vx_adamw_step_ex(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float weight_decay, long step,
+                                float grad_scale, const double* ws, int nws, float max_norm, float* stats, int write_stats, float* ema, float one_minus_decay,
+                                const unsigned char* chunk_group, const float* group_lr, const float* group_wd, int ngroups, void* stream) {
+    VX_REQUIRE(p && g && m && v && n > 0 && step >= 1, "vx_adamw_step_ex: bad args (null pointer, n <= 0 or step < 1)");
+    VX_REQUIRE(!ws || (nws > 0 && nws <= (1 << 16)), "vx_adamw_step_ex: nws must be 1..65536 when ws is given");
+    VX_REQUIRE(!(ws && write_stats) || stats, "vx_adamw_step_ex: write_stats needs the stats buffer");
+    VX_REQUIRE(ngroups >= 0 && ngroups <= VX_ADAMW_MAX_GROUPS, "vx_adamw_step_ex: at most %d param groups", VX_ADAMW_MAX_GROUPS);
+    VX_REQUIRE(!chunk_group || (group_lr && group_wd && ngroups >= 1), "vx_adamw_step_ex: a chunk table needs group_lr, group_wd and ngroups >= 1");
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    VxAdamwGroups grp;
+    for (int k = 0; k < VX_ADAMW_MAX_GROUPS; ++k) {          // (host arrays: they travel as kernel arguments)
+        grp.lr[k] = (chunk_group && k < ngroups) ? group_lr[k] : lr;
+        grp.wd[k] = (chunk_group && k < ngroups) ? group_wd[k] : weight_decay;
+    }
+    const bool al = ((((unsigned long long)p) | ((unsigned long long)g) | ((unsigned long long)m) | ((unsigned long long)v) | ((unsigned long long)ema)) & 15ull) == 0;
+    const long n4 = al ? n >> 2 : 0;
+    float* st_out = (ws && write_stats) ? stats : nullptr;          // to the first launch only
+    if (n4 > 0) {
+        hipLaunchKernelGGL(vx_adamw_ex_k<true>, dim3(vx_cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n4, 0L, lr, beta1, beta2, eps, weight_decay,
+                           (float)bc1, (float)sqrt(bc2), grad_scale, ws, nws, max_norm, st_out, one_minus_decay, chunk_group, grp);
+        st_out = nullptr;
+    }
+    if (n - 4 * n4 > 0)          // unaligned buffers, or the last n % 4 elements
+        hipLaunchKernelGGL(vx_adamw_ex_k<false>, dim3(vx_cdiv(n - 4 * n4, 256)), dim3(256), 0, (hipStream_t)stream, p + 4 * n4, g + 4 * n4, m + 4 * n4, v + 4 * n4,
+                           ema ? ema + 4 * n4 : nullptr, n - 4 * n4, 4 * n4, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale, ws, nws, max_norm,
+                           st_out, one_minus_decay, chunk_group, grp);
+    VX_LAUNCH_CHECK("vx_adamw_step_ex");
     return 0;
 }
 

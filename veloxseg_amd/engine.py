@@ -123,6 +123,8 @@ class FlatParams:
         return out
 
     def zero_grad(self):
+        # Invariant: the 64-element alignment gaps of `grad` hold zeros -- allocated as zeros, zeroed here, and no kernel writes them (every gradient kernel writes
+        # through a parameter's own view) -- so they add nothing to the global gradient norm, which vx_grad_sqnorm_partials takes over whole ranges of the flat buffer
         self.grad.zero_()
 
     def reattach(self):
@@ -374,8 +376,24 @@ class TrainEngine:
 
     def __init__(self, model, criterion, batch_shape, label_dtype=None, lr=2.5e-4, weight_decay=0.01, betas=(0.9, 0.999),
                  eps=1e-8, use_graph=False, overlap=True, process_group=None, warmup_steps=2, verify_replays=3, optimizer=None, fuse_ds=True,
-                 replay="tape", tape_lanes=6, precision="fp32", bucket_min_bytes=1 << 20, level_buckets=False, pipeline_tail=False, force_comm=False):
+                 replay="tape", tape_lanes=6, precision="fp32", bucket_min_bytes=1 << 20, level_buckets=False, pipeline_tail=False, force_comm=False,
+                 max_grad_norm=None, ema_decay=None):
+        """max_grad_norm: clip the AVERAGED gradient (1 / world included) to this global L2 norm inside the optimizer step -- torch.nn.utils.clip_grad_norm_'s formula,
+        resolved on the device (vx_grad_sqnorm_partials + vx_adamw_step_ex: no host synchronisation); `grad_norm` / `clip_coef` / `nonfinite_steps()` report it and
+        flat.grad itself stays unscaled and unclipped.  Every update launch needs every range's partials, so with clipping on the step is NOT pipelined
+        (`pipeline_tail` is ignored: the fourth lane is joined before the norm and the update runs in the unpipelined order).
+        ema_decay: keep e <- e + (1 - decay) (p - e) of every parameter in the same launch (`ema`, ema_state_dict(), ema_weights()); the pipelined split is kept, as it
+        is with several param groups.  With both None and one param group bound the engine allocates nothing for any of this and launches vx_adamw_step as before."""
         self.model, self.criterion = model, criterion
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.ema_decay is not None and not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("ema_decay must be in [0, 1)")
+        self.ema = None                     # flat EMA buffer (laid out as flat.param), allocated below after the data-parallel broadcast
+        self._norm_ws = self._stats = None  # clipping: fp64 partials of sum g^2 / (norm, coefficient, non-finite count, -) on the device
+        self._chunk_group = None            # param groups: device table, one group index per 64 elements of the flat buffers (bind_optimizer)
+        self._group_lr = self._group_wd = None
+        self._ema_swapped, self._ema_tmp = False, None      # ema_weights(): active flag, scratch buffer of the exchange
         # taped data-parallel steps: True = one all-reduce bucket per encoder level, released by markers inside the encoder-backward tape; False
         # (default) = the decoder bucket during the encoder backward, the encoder's gradients in one bucket after it.  A marker joins every forked
         # stream of the stage: measured on one GPU the markers cost 0.85 ms per step (7.50 vs 6.65 ms), more than the ~0.2 ms of all-reduce
@@ -463,6 +481,82 @@ class TrainEngine:
                 except Exception:
                     pass
                 H.call("vx_tape_set_flag_timeout_ms", int(min(max(pg_s or 1800.0, 60.0), 7200.0) * 1000))
+        if self.max_grad_norm is not None:
+            self._norm_ws = torch.zeros(H.query("vx_grad_sqnorm_blocks"), device=self.dev, dtype=torch.float64)
+            self._stats = torch.zeros(4, device=self.dev, dtype=torch.float32)
+        if self.ema_decay is not None:
+            self.ema = self.flat.param.clone()          # (after the broadcast: identical on every rank)
+
+    # ---- clipping statistics / EMA weights --------------------------------------------------------
+    @property
+    def grad_norm(self):
+        """0-dim device view: the last step's global gradient norm BEFORE clipping (of the averaged gradient); None without max_grad_norm.  Reading it synchronises"""
+        return None if self._stats is None else self._stats[0]
+
+    @property
+    def clip_coef(self):
+        """0-dim device view: the coefficient the last step multiplied its gradient by (1.0 = not clipped)"""
+        return None if self._stats is None else self._stats[1]
+
+    def nonfinite_steps(self) -> int:
+        """steps whose gradient norm was inf / NaN so far (they are applied as torch applies them with error_if_nonfinite=False: nothing is skipped).  Synchronises"""
+        return 0 if self._stats is None else int(self._stats[2])
+
+    def _named_ema(self):
+        for n in self.flat.names:
+            o, k = self.flat.slices[n]
+            yield n, o, k
+
+    def ema_state_dict(self):
+        """the EMA weights under the model's state_dict keys (cloned); buffers and frozen parameters are the model's own"""
+        if self.ema is None:
+            raise RuntimeError("TrainEngine was built without ema_decay")
+        self.flush()
+        shapes = dict(zip(self.flat.names, (p.shape for p in self.flat.params)))
+        out = type(self.model.state_dict())()
+        for k_, v_ in self.model.state_dict().items():
+            if k_ in self.flat.slices:
+                o, k = self.flat.slices[k_]
+                out[k_] = self.ema[o:o + k].view(shapes[k_]).clone()
+            else:
+                out[k_] = v_.detach().clone()
+        return out
+
+    def load_ema_state_dict(self, sd):
+        if self.ema is None:
+            raise RuntimeError("TrainEngine was built without ema_decay")
+        missing = [n for n in self.flat.names if n not in sd]
+        if missing:
+            raise KeyError(f"EMA state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+        self.flush()
+        for n, o, k in self._named_ema():
+            self.ema[o:o + k].copy_(sd[n].reshape(-1))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters hold the EMA weights: the CONTENTS of flat.param and of the EMA buffer are exchanged on the device (and exchanged back
+        on exit) -- no copy of the model, no re-homed pointers (tapes bake raw pointers in).  functional.weights_epoch_bump() on the way in and out, so a TapedPredictor
+        of this model re-captures its weight images.  step() inside the context raises (it would train the EMA as if it were the parameters); the context does not nest."""
+        if self.ema is None:
+            raise RuntimeError("TrainEngine was built without ema_decay")
+        if self._ema_swapped:
+            raise RuntimeError("TrainEngine.ema_weights() is already active")
+        if self._ema_tmp is None:
+            self._ema_tmp = torch.empty_like(self.ema)          # scratch of the exchange, kept: no allocation on later entries
+
+        def swap():
+            VF.weights_epoch_bump()
+            self._ema_tmp.copy_(self.flat.param)
+            self.flat.param.copy_(self.ema)
+            self.ema.copy_(self._ema_tmp)
+        self.flush()
+        swap()
+        self._ema_swapped = True
+        try:
+            yield self.model
+        finally:
+            self._ema_swapped = False
+            swap()
 
     @contextlib.contextmanager
     def _settings(self, capture: bool = False):
@@ -572,7 +666,9 @@ class TrainEngine:
     # The braces run concurrently on one HIP stream per branch.  Eagerly the same functions run back to back (stage order is
     # a valid serialisation), which is the reference the captured graphs are checked against.
     def _pipe_active(self):
-        return bool(self.pipeline_tail and self.use_graph and self.replay_mode == "tape" and not self.level_buckets and self._split_dec_wgrad())
+        # (clipping: every update launch needs every range's partials -- the encoder half's coefficient depends on the decoder gradients -- so the step is not pipelined)
+        return bool(self.pipeline_tail and self.max_grad_norm is None and self.use_graph and self.replay_mode == "tape" and not self.level_buckets
+                    and self._split_dec_wgrad())
 
     def _s_enc_fwd(self):
         if self._pipe_active():
@@ -931,10 +1027,27 @@ class TrainEngine:
         optimizer.load_state_dict()."""
         if not isinstance(optimizer, torch.optim.AdamW):
             raise TypeError("TrainEngine drives torch.optim.AdamW only (the optimizer of every shipped train_config)")
-        if len(optimizer.param_groups) != 1 or sorted(id(p) for p in optimizer.param_groups[0]["params"]) != sorted(id(p) for p in self.flat.params):
-            raise ValueError("optimizer must hold exactly model.parameters() in one param group")
-        if optimizer.param_groups[0].get("amsgrad") or optimizer.param_groups[0].get("maximize"):
+        groups = optimizer.param_groups
+        if len(groups) > 8:
+            raise ValueError("the fused AdamW takes at most 8 param groups")
+        if sorted(id(p) for g in groups for p in g["params"]) != sorted(id(p) for p in self.flat.params):
+            raise ValueError("the optimizer's param groups must partition exactly model.parameters()")
+        if any(g.get("amsgrad") or g.get("maximize") for g in groups):
             raise NotImplementedError("amsgrad / maximize are not supported by the fused AdamW")
+        if any(tuple(g["betas"]) != tuple(groups[0]["betas"]) or g["eps"] != groups[0]["eps"] for g in groups[1:]):
+            raise NotImplementedError("the fused AdamW shares betas and eps between param groups (lr and weight_decay are per group)")
+        self._chunk_group = self._group_lr = self._group_wd = None
+        if len(groups) > 1:
+            # one group index per 64-element chunk of the flat buffers, built once per bind (FlatParams aligns every parameter to 64 elements: a chunk never spans
+            # two parameters; the chunks of an alignment gap belong to the parameter in front of it -- their gradient and moments are zero)
+            import ctypes
+            gid = {id(p): gi for gi, g in enumerate(groups) for p in g["params"]}
+            table = torch.zeros(self.flat.numel // 64, dtype=torch.uint8)
+            for n, p in zip(self.flat.names, self.flat.params):
+                o, k = self.flat.slices[n]
+                table[o // 64:_align(o + k) // 64] = gid[id(p)]
+            self._chunk_group = table.to(self.dev)
+            self._group_lr, self._group_wd = (ctypes.c_float * 8)(), (ctypes.c_float * 8)()      # host arrays: refreshed every step (_adamw_begin), copied into the kernel arguments
         self.optimizer = optimizer
         self.load_optimizer_state()
 
@@ -963,20 +1076,38 @@ class TrainEngine:
         if self.optimizer is not None:
             g = self.optimizer.param_groups[0]
             self.lr, self.wd, self.betas, self.eps = g["lr"], g["weight_decay"], g["betas"], g["eps"]
+            if self._chunk_group is not None:        # lr / weight_decay per group, every step: schedulers keep working
+                for k, gk in enumerate(self.optimizer.param_groups):
+                    self._group_lr[k], self._group_wd[k] = gk["lr"], gk["weight_decay"]
             self._step_tensor += 1
             self.optimizer._opt_called = True        # the fused kernel below IS optimizer.step(); keeps LR schedulers from warning
         self.t += 1
 
-    def _adamw_range(self, lo, hi):
-        """the fused update of flat[lo:hi] on the current stream (element-wise: any slice of the flat buffers)"""
+    def _adamw_range(self, lo, hi, write_stats=False):
+        """the fused update of flat[lo:hi] on the current stream (element-wise: any slice of the flat buffers; lo is a multiple of 64)"""
         if hi <= lo:
             return
-        H.call("vx_adamw_step", H.P(self.flat.param[lo:hi]), H.P(self.flat.grad[lo:hi]), H.P(self.m[lo:hi]), H.P(self.v[lo:hi]), int(hi - lo), float(self.lr),
-               float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), self.t, 1.0 / self.world, H.stream_ptr())
+        if self._norm_ws is None and self.ema is None and self._chunk_group is None:
+            H.call("vx_adamw_step", H.P(self.flat.param[lo:hi]), H.P(self.flat.grad[lo:hi]), H.P(self.m[lo:hi]), H.P(self.v[lo:hi]), int(hi - lo), float(self.lr),
+                   float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), self.t, 1.0 / self.world, H.stream_ptr())
+            return
+        import ctypes
+        clip, grp = self._norm_ws is not None, self._chunk_group is not None
+        H.call("vx_adamw_step_ex", H.P(self.flat.param[lo:hi]), H.P(self.flat.grad[lo:hi]), H.P(self.m[lo:hi]), H.P(self.v[lo:hi]), int(hi - lo), float(self.lr),
+               float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), self.t, 1.0 / self.world,
+               H.P(self._norm_ws, torch.float64) if clip else None, int(self._norm_ws.numel()) if clip else 0, float(self.max_grad_norm) if clip else 0.0,
+               H.P(self._stats) if clip else None, int(bool(write_stats)),
+               H.P(self.ema[lo:hi]) if self.ema is not None else None, (1.0 - self.ema_decay) if self.ema is not None else 0.0,
+               (H.P(self._chunk_group, torch.uint8) + lo // 64) if grp else None, ctypes.addressof(self._group_lr) if grp else None,
+               ctypes.addressof(self._group_wd) if grp else None, len(self.optimizer.param_groups) if grp else 0, H.stream_ptr())
 
     def _adamw(self):
+        """the whole update on the current stream, behind every gradient: with clipping one launch for the partials of sum g^2 over the whole flat gradient (alignment
+        gaps are zero: FlatParams.zero_grad), then the update, which finalises the norm itself"""
         self._adamw_begin()
-        self._adamw_range(0, self.flat.numel)
+        if self._norm_ws is not None:
+            H.call("vx_grad_sqnorm_partials", H.P(self.flat.grad), int(self.flat.numel), H.P(self._norm_ws, torch.float64), H.stream_ptr())
+        self._adamw_range(0, self.flat.numel, write_stats=True)
 
     def _check_flag_timeouts(self):
         if self.replay_mode == "tape":
@@ -1256,6 +1387,8 @@ class TrainEngine:
     # ---- public ---------------------------------------------------------------------------------
     def step(self, x: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimisation step.  x / labels are copied into the engine's static buffers (None = reuse their contents)."""
+        if self._ema_swapped:
+            raise RuntimeError("TrainEngine.step() inside ema_weights(): the parameters hold the EMA weights; leave the context first")
         if x is not None:
             self.x.copy_(x, non_blocking=True)
         if labels is not None:

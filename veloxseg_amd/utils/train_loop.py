@@ -10,6 +10,7 @@ any iterable of (inputs, labels) batches; `SyntheticPatches` is the stand-in use
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 import time
@@ -119,9 +120,10 @@ def run_train(args, train_config, model_config, train_loader: Optional[Iterable]
     training_scheduler = build_scheduler(optimizer=optimizer, scheduler_type="training_scheduler", config=train_config)
     warmup_epoch = train_config["warmup_scheduler"]["warmup_epochs"]
     start_epoch, best_train_dice, best_val_dice = 0, 0, 0
+    ckpt_extras = {}                 # what the checkpoint holds beyond the reference's keys ("ema"), from the same read
     if getattr(args, "checkpoint_path", None) is not None:
         model, optimizer, warmup_scheduler, training_scheduler, start_epoch, best_train_dice, best_val_dice = load_checkpoint(
-            model, args.checkpoint_path, optimizer, warmup_scheduler, training_scheduler, device)
+            model, args.checkpoint_path, optimizer, warmup_scheduler, training_scheduler, device, extras=ckpt_extras)
         log.info("Load Checkpoint, Continue to Train!!!!")
     batch = train_config["batch_size"]
     import torch.distributed as dist
@@ -134,15 +136,28 @@ def run_train(args, train_config, model_config, train_loader: Optional[Iterable]
     # engine buffers from the configuration, not from a pulled batch (that would consume one batch of a one-shot iterable and spin up an extra
     # worker pool); loaders must yield (batch_size, sum(in_ch), *input_size) inputs -- labels of any integer dtype are converted by the copy
     size = list(mcfg["input_size"])
+    # beyond the reference: global-norm gradient clipping and EMA weights inside the fused optimizer step
+    max_grad_norm = train_config["optimizer"].get("max_grad_norm")
+    ema_cfg = train_config.get("ema") or {}
     x_shape = (batch, sum(mcfg["in_ch"]), *size)
     # per-head metrics (show_deep_metric) need every head at full resolution in engine.last_outputs: then the up-sampling is not fused into the loss
     engine = TrainEngine(model, criterion, x_shape, label_dtype=None, optimizer=optimizer, use_graph=getattr(args, "use_graph", False),
                          fuse_ds=not train_config.get("show_deep_metric", False), precision=getattr(args, "precision", "fp32"),
-                         pipeline_tail=getattr(args, "pipeline_tail", False))  # (opt-in: the decoder tail of step N beside the encoder forward of step N + 1; flush() below)
+                         pipeline_tail=getattr(args, "pipeline_tail", False),  # (opt-in: the decoder tail of step N beside the encoder forward of step N + 1; flush() below)
+                         max_grad_norm=max_grad_norm, ema_decay=ema_cfg.get("decay"))
+    if engine.ema is not None and getattr(args, "checkpoint_path", None) is not None:
+        if ckpt_extras.get("ema") is not None:
+            engine.load_ema_state_dict(ckpt_extras["ema"])
+            log.info("EMA weights restored from the checkpoint")
+        else:
+            log.warning("train_config[\"ema\"] is set but %s holds no \"ema\" entry: the EMA restarts from the loaded weights", args.checkpoint_path)
+    ema_of = (lambda: engine.ema_state_dict()) if engine.ema is not None else (lambda: None)
     show_deep_metrics = _metric_fns(args.dataset_name)
     not_pred = 2 + num_modal if args.model_name == "VeloxSeg" else 0
     sched_type = train_config["train_scheduler"]["scheduler_type"]
     hist = {"loss": [], "lr": [], "dice": [], "val_dice": [], "checkpoints": []}
+    if max_grad_norm is not None:
+        hist["grad_norm"] = []
     if save_path:
         os.makedirs(save_path, exist_ok=True)
     for epoch in range(start_epoch, train_config["epochs"]):
@@ -170,19 +185,23 @@ def run_train(args, train_config, model_config, train_loader: Optional[Iterable]
         mean_loss, mean_dice = total_loss / max(nsteps, 1), total_dice / max(nsteps, 1)
         hist["loss"].append(mean_loss)
         hist["dice"].append(mean_dice)
+        if max_grad_norm is not None:
+            hist["grad_norm"].append(float(engine.grad_norm))      # the last step's pre-clip norm: ONE host read per epoch (the steps themselves read nothing back)
         if save_path and epoch % train_config["save_model_interval"] == 0:
             f = os.path.join(save_path, f"{epoch}.pth")
-            save_checkpoint(model, optimizer, warmup_scheduler, training_scheduler, epoch, best_train_dice, best_val_dice, f)
+            save_checkpoint(model, optimizer, warmup_scheduler, training_scheduler, epoch, best_train_dice, best_val_dice, f, ema=ema_of())
             hist["checkpoints"].append(f)
         if mean_dice >= best_train_dice:
             best_train_dice = mean_dice
             if save_path:
-                save_checkpoint(model, optimizer, warmup_scheduler, training_scheduler, epoch, best_train_dice, best_val_dice, os.path.join(save_path, "train_best.pth"))
+                save_checkpoint(model, optimizer, warmup_scheduler, training_scheduler, epoch, best_train_dice, best_val_dice, os.path.join(save_path, "train_best.pth"), ema=ema_of())
         log.info(f"training epoch {epoch + 1}: loss {mean_loss:.4f} dice {mean_dice:.4f} best {best_train_dice:.4f} time {time.time() - start:.2f} s")
         if val_loader is not None and (epoch + 1) % train_config["val_interval"] == 0:
             model.eval()
             tot, n = 0.0, 0
-            with torch.no_grad():
+            # train_config["ema"]["validate"]: the validation forward reads the EMA weights (swapped in place for the duration: TrainEngine.ema_weights)
+            ema_ctx = engine.ema_weights() if (engine.ema is not None and ema_cfg.get("validate")) else contextlib.nullcontext()
+            with ema_ctx, torch.no_grad():
                 for inputs, labels in val_loader:
                     out = model(inputs)
                     metrics, _ = show_deep_metrics(out, labels, False)
@@ -199,6 +218,6 @@ def run_train(args, train_config, model_config, train_loader: Optional[Iterable]
             if val_dice >= best_val_dice:
                 best_val_dice = val_dice
                 if save_path:
-                    save_checkpoint(model, optimizer, warmup_scheduler, training_scheduler, epoch, best_train_dice, best_val_dice, os.path.join(save_path, "val_best.pth"))
+                    save_checkpoint(model, optimizer, warmup_scheduler, training_scheduler, epoch, best_train_dice, best_val_dice, os.path.join(save_path, "val_best.pth"), ema=ema_of())
     hist.update(best_train_dice=best_train_dice, best_val_dice=best_val_dice, engine=engine)
     return hist
