@@ -362,7 +362,11 @@ typedef struct VxPwaPlan {
 int vx_pwa_gather_fwd(const float* src, float* tok, const VxPwaPlan* plan, int c, int m, int M, int B, void* stream);
 int vx_pwa_gather_bwd(const float* src, const float* dtok, float* dsrc, const VxPwaPlan* plan, int c, int m, int M, int B, void* stream);
 /* the same gather for ALL 3*M tensors (q0,k0,v0,q1,...) in ONE launch; the arg-max voxel of every pooled cell is saved (int32, token layout) and
- * drives the backward pass (srcs / dsrcs: host arrays of 3*M device pointers) */
+ * drives the backward pass (srcs / dsrcs: host arrays of 3*M device pointers).
+ * Pooling rule of all gather entries = aten max_pool3d: scan the cell in (d, h, w) order and update on `val > best || isnan(val)`.  So the FIRST maximum wins a tie
+ * (-0.0 == +0.0: the earlier one, with its sign), an all -inf cell yields -inf at its first voxel, and a cell that holds a NaN yields NaN with the index of its
+ * LAST NaN.  The index is the flattened (d * H + h) * W + w of the channel's volume.  The channel-vectorised kernels write no index for 1 x 1 x 1 cells (the
+ * backward knows the arg-max is the voxel itself).  tests/test_pwa_exact_gpu.py holds every form to F.max_pool3d(return_indices=True) bit for bit. */
 int vx_pwa_gather_all_fwd(const float* const* srcs, float* tq, float* tk, float* tv, int* iq, int* ik, int* iv,
                           const VxPwaPlan* plan, int cq, int cv, int M, int B, void* stream);
 int vx_pwa_gather_all_bwd(const float* dtq, const float* dtk, const float* dtv, const int* iq, const int* ik, const int* iv, float* const* dsrcs,

@@ -102,8 +102,18 @@ __global__ void __launch_bounds__(256) vx_pwa_gather_bwd_k(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // fused gather of ALL q/k/v tensors of ALL modalities in one launch, arg-max saved for the backward pass.
 //   A pooled cell (s0*s1*s2 voxels) is reduced cooperatively by T = min(64, cell size) adjacent lanes (shuffle reduction with the
-//   aten tie rule: first index wins), so the coarse scales (8^3 = 512 voxels per cell) no longer serialise in one thread.
+//   aten rule, vx_pool_takes: first maximum wins, a NaN propagates and the last NaN's index is saved), so the coarse scales (8^3 = 512 voxels per cell) no longer
+//   serialise in one thread.
 // ---------------------------------------------------------------------------------------------
+// The pooling rule is aten's max_pool3d scan `val > best || isnan(val)` over the cell in (d, h, w) order: the first maximum wins a tie, a cell that holds a NaN yields
+// NaN, and the saved index is then the LAST NaN of the scan.  A lane scans its own elements in increasing index order with that rule; two lanes' partial results
+// (value, index) combine as below: a NaN side beats a number, of two NaNs the larger index stays, of two numbers the larger value and, on a tie, the smaller index.
+// (A lane without elements holds (-inf, INT_MAX) and loses every tie.)
+__device__ __forceinline__ bool vx_pool_takes(float ov, int oi, float best, int bidx) {
+    if (ov != ov) return best == best || oi > bidx;
+    return best == best && (ov > best || (ov == best && oi < bidx));
+}
+
 struct VxGatherPtrs {
     const float* src[12];   // q0,k0,v0,q1,k1,v1,...
     float* dsrc[12];
@@ -144,12 +154,12 @@ __global__ void __launch_bounds__(256) vx_pwa_gather_all_fwd_k(VxGatherPtrs ptrs
         const int w = e % s2, h = (e / s2) % s1, d = e / (s2 * s1);
         const int idx = ((p0 * s0 + d) * P.grid[1] + (p1 * s1 + h)) * P.grid[2] + (p2 * s2 + w);
         const float val = sc[idx];
-        if (val > best || bidx == 0x7fffffff) { best = val; bidx = idx; }     // increasing idx per lane: strict > keeps the first
+        if (val > best || val != val || bidx == 0x7fffffff) { best = val; bidx = idx; }     // increasing idx per lane: strict > keeps the first maximum, a NaN always updates (the last one stays)
     }
     for (int o = T >> 1; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bidx, o, 64);
-        if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+        if (vx_pool_takes(ov, oi, best, bidx)) { best = ov; bidx = oi; }
     }
     if (cok && sub == 0) {
         const int W0 = p0 / P.n[0], t0 = p0 % P.n[0], W1 = p1 / P.n[1], t1 = p1 % P.n[1], W2 = p2 / P.n[2], t2 = p2 % P.n[2];
@@ -233,22 +243,47 @@ __global__ void __launch_bounds__(256) vx_pwa_gather_all_fwd_v_k(VxGatherPtrs pt
     for (int k = 0; k < CH; ++k) { best[k] = -INFINITY; bidx[k] = 0x7fffffff; }
     const VxFd f2 = vx_fd(s2), f1 = vx_fd(s1);
     const int base = (p0 * s0 * P.grid[1] + p1 * s1) * P.grid[2] + p2 * s2;
-    for (int e = sub; e < csz; e += T) {
+    auto voxel = [&](int e) {
         int w, h;
         const int d = vx_fdivmod(vx_fdivmod(e, f2, w), f1, h);
-        const int idx = base + (d * P.grid[1] + h) * P.grid[2] + w;
+        return base + (d * P.grid[1] + h) * P.grid[2] + w;
+    };
+    if (sub < csz) {
+        // the lane's first element is taken as it comes (-inf and NaN included): cells up to 64 voxels, one element per lane, compare nothing here
+        const int first = voxel(sub);
 #pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const float val = sc[(long)k * V + idx];
-            if (val > best[k] || bidx[k] == 0x7fffffff) { best[k] = val; bidx[k] = idx; }     // increasing idx per lane: strict > keeps the first
+        for (int k = 0; k < CH; ++k) { best[k] = sc[(long)k * V + first]; bidx[k] = first; }
+        for (int e = sub + T; e < csz; e += T) {
+            const int idx = voxel(e);
+#pragma unroll
+            for (int k = 0; k < CH; ++k) {
+                const float val = sc[(long)k * V + idx];
+                if (val > best[k] || val != val) { best[k] = val; bidx[k] = idx; }     // increasing idx per lane: strict > keeps the first maximum, a NaN always updates (the last one stays)
+            }
         }
     }
-    for (int o = T >> 1; o > 0; o >>= 1) {
+    // this kernel is bound by its compares and shuffles, not by memory: the NaN-aware combine measured +11 % on the launch (32^3 grid, four scales: 38.8 -> 43.2 us).
+    // A wave whose lanes met no NaN -- wave-uniform, and all but always the case -- takes the plain combine, to which vx_pool_takes reduces without NaNs.
+    bool met_nan = false;
 #pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const float ov = __shfl_xor(best[k], o, 64);
-            const int oi = __shfl_xor(bidx[k], o, 64);
-            if (ov > best[k] || (ov == best[k] && oi < bidx[k])) { best[k] = ov; bidx[k] = oi; }
+    for (int k = 0; k < CH; ++k) met_nan = met_nan || best[k] != best[k];
+    if (!__any(met_nan)) {
+        for (int o = T >> 1; o > 0; o >>= 1) {
+#pragma unroll
+            for (int k = 0; k < CH; ++k) {
+                const float ov = __shfl_xor(best[k], o, 64);
+                const int oi = __shfl_xor(bidx[k], o, 64);
+                if (ov > best[k] || (ov == best[k] && oi < bidx[k])) { best[k] = ov; bidx[k] = oi; }
+            }
+        }
+    } else {
+        for (int o = T >> 1; o > 0; o >>= 1) {
+#pragma unroll
+            for (int k = 0; k < CH; ++k) {
+                const float ov = __shfl_xor(best[k], o, 64);
+                const int oi = __shfl_xor(bidx[k], o, 64);
+                if (vx_pool_takes(ov, oi, best[k], bidx[k])) { best[k] = ov; bidx[k] = oi; }
+            }
         }
     }
     if (cok && sub == 0) {
@@ -380,7 +415,11 @@ struct VxScPtrs { const float* in[4]; float* out[4]; };
 // (round 6) the window ranges of the scales whose adjoint kernels ADD with atomics: the identity-scale kernel, which runs first on the stream, zeroes them (no separate fill launch)
 struct VxScZero { int n; int w0[4], wn[4]; int assign; float* extra; long extra_n4; };      // extra: one more buffer the identity-scale kernel zeroes (float4 units; the attention backward's bias-gradient replicas)
 
+// ratio, position and lambda as aten's align_corners=True and oracle.interp_matrix form them: s = ratio * j is ROUNDED to fp32 before lam = s - i0.  Contracted into
+// fma(ratio, j, -i0) -- the compiler's default for HIP -- lam is the unrounded residual: off by up to half an ulp of s (4 u at s = 7, seen as 45 u S in the scatter
+// forward), and slightly NEGATIVE where s rounds up to an integer, so that a neighbour token with weight 0 enters the sum.  Hence no contraction in this function.
 __device__ __forceinline__ void vx_src_coord(int j, int n, int bw, int& i0, int& i1, float& lam) {
+#pragma clang fp contract(off)
     if (bw == n) { i0 = j; i1 = j; lam = 0.0f; return; }
     const float ratio = (float)(n - 1) / (float)(bw - 1);
     const float s = ratio * (float)j;
