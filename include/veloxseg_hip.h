@@ -565,6 +565,22 @@ int vx_sw_mirror_sum(const float* pred, float* wsum, long rows, int rd, int rh, 
  * by vx_sw_accumulate.  One call per window, in the reference's window order. */
 int vx_sw_mirror_accumulate(const float* pred, const float* wsum, float* acc, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0,
                             int mask, float weight, void* stream);
+/* ---- Gaussian importance blending of the sliding window (utils/inference_runtime.py, blend="gaussian") ----
+ * The weight of a window voxel is w[z, y, x] = max(fl(fl(g_0[z] * g_1[y]) * g_2[x]), floor): three axis tables made on the host, floor > 0.  g: DEVICE pointer to
+ * their rd + rh + rw floats, one after the other.  No weight volume and no count volume exists: both kernels form w in registers.  Arguments are checked before any launch (-1).
+ *
+ * acc[:, window] += w * p for ONE window, p = the mirrored-back pred (wsum NULL: weight is not used) or weight * (wsum + mirrored-back pred) (wsum given: the last
+ * mirror's add of a test-time augmentation, as in vx_sw_mirror_accumulate).  pred, wsum: (C, rd, rh, rw); acc: (C, D, H, W).  The sum, weight *, w * and the accumulation
+ * are rounded one after the other (no fma).  One call per window, in window order.  Four voxels along x per thread under the conditions of the mirror kernels.  rh * rw and C * rd <= 2^30. */
+int vx_sw_blend_accumulate(const float* pred, const float* wsum, float* acc, const float* g, float floor, int C, int D, int H, int W, int rd, int rh, int rw,
+                           int z0, int y0, int x0, int mask, float weight, void* stream);
+/* out = acc / cnt in IEEE fp32 (out may alias acc or be NULL), labels as in vx_sw_finalize (may be NULL; not both).  cnt[v] = sum of w over the windows that cover v,
+ * added one after the other from 0 in ascending window index (iz * ny + iy) * nx + ix, formed per voxel on the fly from per-axis tables made on the host:
+ * tab: DEVICE pointer to D + H + W ints, the number of windows that cover each coordinate of the three axes; gc: DEVICE pointer to D * cz + H * cy + W * cx floats,
+ * GZ[D][cz] GY[H][cy] GX[W][cx], row c = the axis-table values g_a[c - start] of the windows that cover coordinate c, in ascending start; cz, cy, cx = the row strides
+ * (the largest count of each axis).  The kernel clamps a count to 0 .. stride: a wrong table gives wrong numbers, never a read outside tab and gc.  H * W <= 2^30. */
+int vx_sw_blend_finalize(const float* acc, float* out, unsigned char* labels, const float* gc, float floor, const int* tab, int cz, int cy, int cx,
+                         int C, int D, int H, int W, void* stream);
 /* labels[b, v] = argmax_c logits[b, c, v] (first maximum, uint8): `outputs[0].argmax(dim=1)` of utils/metric/metrics.py:16 */
 int vx_argmax_channels(const float* logits, unsigned char* labels, int B, int C, long V, void* stream);
 /* conf[b, g, p] += #voxels with ground truth g and prediction p (uint64, NC*NC per sample; caller zeroes it): the sufficient statistic of

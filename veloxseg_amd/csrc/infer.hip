@@ -138,6 +138,112 @@ __global__ void __launch_bounds__(256) vx_sw_mirror_accumulate_k(const float* __
     }
 }
 
+// ---- Gaussian importance blending (utils/inference_runtime.py, blend="gaussian") -------------------------------------------
+// The weight of a window voxel is w[z, y, x] = max((g[z] * g[rd + y]) * g[rd + rh + x], floor): three host-made axis tables behind one pointer and a clamp that makes
+// w non-separable.  It is formed in registers from the tables (a few hundred floats, cache-resident), never stored as a volume; both products are rounded.
+// The weights are not powers of two, so acc + w * p contracted into an fma is NOT the bits of the product followed by the sum.  This toolchain's __fmul_rn / __fadd_rn are
+// the plain operators and are contracted like them (the section-21 kernels above only ever scale by a power of two, where the fma gives the same bits); the operators
+// below are emitted under `fp contract(off)` and stay a v_mul_f32 and a v_add_f32.
+__device__ __forceinline__ float vx_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float vx_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float vx_blend_w(float gzy, float gx, float floor) { return fmaxf(vx_mul_rn(gzy, gx), floor); }
+
+// acc[c, z0+z, y0+y, x0+x] += w[z, y, x] * p,  p = pred[c, m_z(z), m_y(y), m_x(x)] (MIRROR false: wsum is not read) or weight * (wsum[c, z, y, x] + that) (MIRROR true):
+// vx_sw_mirror_accumulate_k with the window weight in front.  Every operation rounds on its own, in this order: the sum, weight *, w *, the accumulation.
+// blockIdx.y walks the C * rd planes of the window, so channel, z and g[z] are uniform (scalar registers) and a thread splits its index inside the (rh, rw / V) plane
+// with one 32-bit division; the lanes of a wave cover consecutive x of a row, as in the kernels above.
+template <int V, bool MIRROR>
+__global__ void __launch_bounds__(256) vx_sw_blend_accumulate_k(const float* __restrict__ pred, const float* __restrict__ wsum, float* __restrict__ acc,
+                                                                const float* __restrict__ g, float floor, VxWin P, int mask, float weight) {
+    const int rwv = P.rw / V;
+    const int plane = P.rh * rwv, planes = P.C * P.rd;
+    const long pstride = (long)P.rh * P.rw;
+    const float* __restrict__ gy = g + P.rd;
+    const float* __restrict__ gx = gy + P.rh;
+    for (int p = blockIdx.y; p < planes; p += gridDim.y) {
+        const int c = p / P.rd, z = p - c * P.rd;
+        const int zs = (mask & 1) ? P.rd - 1 - z : z;
+        const float gz = g[z];
+        const float* __restrict__ src = pred + ((long)c * P.rd + zs) * pstride;
+        const float* __restrict__ sum = MIRROR ? wsum + (long)p * pstride : nullptr;
+        float* __restrict__ dst = acc + (((long)c * P.D + P.z0 + z) * P.H + P.y0) * P.W + P.x0;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < plane; i += gridDim.x * 256) {
+            const int y = i / rwv, xg = i - y * rwv;
+            const int ys = (mask & 2) ? P.rh - 1 - y : y, xs = (mask & 4) ? P.rw - V - xg * V : xg * V;
+            const long s = (long)ys * P.rw + xs;
+            const long a = (long)y * P.W + xg * V;
+            const float gzy = vx_mul_rn(gz, gy[y]);
+            if (V == 4) {
+                float4 v = vx_rev4(vx_ld4(src, s), mask & 4);
+                if (MIRROR) {
+                    const float4 o = vx_ld4(sum, (long)i * 4);
+                    v = make_float4(vx_mul_rn(weight, vx_add_rn(o.x, v.x)), vx_mul_rn(weight, vx_add_rn(o.y, v.y)), vx_mul_rn(weight, vx_add_rn(o.z, v.z)), vx_mul_rn(weight, vx_add_rn(o.w, v.w)));
+                }
+                const float4 q = vx_ld4(dst, a);
+                const float* __restrict__ gq = gx + xg * 4;
+                vx_st4(dst, a, make_float4(vx_add_rn(q.x, vx_mul_rn(vx_blend_w(gzy, gq[0], floor), v.x)), vx_add_rn(q.y, vx_mul_rn(vx_blend_w(gzy, gq[1], floor), v.y)),
+                                           vx_add_rn(q.z, vx_mul_rn(vx_blend_w(gzy, gq[2], floor), v.z)), vx_add_rn(q.w, vx_mul_rn(vx_blend_w(gzy, gq[3], floor), v.w))));
+            } else {
+                float v = src[s];
+                if (MIRROR) v = vx_mul_rn(weight, vx_add_rn(sum[i], v));
+                dst[a] = vx_add_rn(dst[a], vx_mul_rn(vx_blend_w(gzy, gx[xg], floor), v));
+            }
+        }
+    }
+}
+
+// What the normaliser of a volume geometry needs, made on the host per axis: for every coordinate the number of windows that cover it (tab: n_z[D] n_y[H] n_x[W]) and
+// the axis-table values of those windows in ascending window start (gc: GZ[D][cz] GY[H][cy] GX[W][cx], GZ[z][j] = g_0[z - (j-th covering start)]; cz / cy / cx = the
+// largest count of the axis, the row stride).
+struct VxBlendGeom { int C, D, H, W, cz, cy, cx; };
+
+// out[c, v] = acc[c, v] / cnt[v] (may alias acc), labels[v] = first arg-max as in vx_sw_finalize_k; cnt[v] = the sum of w over the windows that cover v, added one after the
+// other from 0 in ascending window index (iz * ny + iy) * nx + ix -- z outermost, x innermost -- which is the order the windows were accumulated in.  One thread per
+// voxel, no atomics, nothing shared between threads: the same bits every run.  blockIdx.y walks z (uniform: its count and table row sit in scalar registers), a thread
+// splits its index inside the (H, W) plane with one 32-bit division.  A count outside 0 .. stride is clamped: a wrong table gives wrong numbers, never a read outside it.
+__global__ void __launch_bounds__(256) vx_sw_blend_finalize_k(const float* acc, float* out, unsigned char* __restrict__ labels, const float* __restrict__ gc, float floor,
+                                                              const int* __restrict__ tab, VxBlendGeom P) {
+    const int plane = P.H * P.W;
+    const long V = (long)P.D * plane;
+    const int* __restrict__ tz = tab;
+    const int* __restrict__ ty = tz + P.D;
+    const int* __restrict__ tx = ty + P.H;
+    const float* __restrict__ GZ = gc;
+    const float* __restrict__ GY = GZ + (long)P.D * P.cz;
+    const float* __restrict__ GX = GY + (long)P.H * P.cy;
+    for (int z = blockIdx.y; z < P.D; z += gridDim.y) {
+        const int nz = min(max(tz[z], 0), P.cz);
+        const float* __restrict__ gz = GZ + (long)z * P.cz;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < plane; i += gridDim.x * 256) {
+            const int y = i / P.W, x = i - y * P.W;
+            const int ny = min(max(ty[y], 0), P.cy), nx = min(max(tx[x], 0), P.cx);
+            const float* __restrict__ gy = GY + (long)y * P.cy;
+            const float* __restrict__ gx = GX + (long)x * P.cx;
+            float cnt = 0.f;
+            for (int jz = 0; jz < nz; ++jz)
+                for (int jy = 0; jy < ny; ++jy) {
+                    const float gzy = vx_mul_rn(gz[jz], gy[jy]);
+                    for (int jx = 0; jx < nx; ++jx) cnt = vx_add_rn(cnt, vx_blend_w(gzy, gx[jx], floor));
+                }
+            const long v = (long)z * plane + i;
+            float best = -INFINITY;
+            int arg = 0;
+            for (int c = 0; c < P.C; ++c) {
+                const float q = acc[(long)c * V + v] / cnt;
+                if (out) out[(long)c * V + v] = q;
+                if (q > best || (q != q && !(best != best))) { best = q; arg = c; }    // NaN ranks highest, first occurrence wins (aten)
+            }
+            if (labels) labels[v] = (unsigned char)arg;
+        }
+    }
+}
+
 // labels[b, v] = argmax_c logits[b, c, v]  (uint8; first maximum)
 __global__ void __launch_bounds__(256) vx_argmax_k(const float* __restrict__ logits, unsigned char* __restrict__ labels, int C, long V) {
     const long b = blockIdx.y;
@@ -256,6 +362,47 @@ extern "C" int vx_sw_mirror_accumulate(const float* pred, const float* wsum, flo
         vx_sw_mirror_accumulate_k<4><<<dim3(vx_stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(pred, wsum, acc, P, mask, weight);
     else vx_sw_mirror_accumulate_k<1><<<dim3(vx_stream_grid(n)), dim3(256), 0, (hipStream_t)stream>>>(pred, wsum, acc, P, mask, weight);
     VX_LAUNCH_CHECK("vx_sw_mirror_accumulate");
+    return 0;
+}
+
+// grid of the plane-walking kernels above: x over the 256-thread chunks of a plane (at most 16), y over the planes, about 2048 blocks in all, the rest by the stride
+// loops; both extents are levelled so that every block takes the same number of turns (9 chunks: 9 blocks of one turn, not 8 of two)
+static inline long vx_level(long n, long cap) { const long turns = (n + cap - 1) / cap; return (n + turns - 1) / turns; }
+static inline dim3 vx_plane_grid(long plane, long planes) {
+    const long chunks = plane > 256 ? (plane + 255) / 256 : 1;
+    const long gx = vx_level(chunks, 16);
+    const long gy = vx_level(planes < 1 ? 1 : planes, 2048 / gx);
+    return dim3((unsigned)gx, (unsigned)gy);
+}
+
+extern "C" int vx_sw_blend_accumulate(const float* pred, const float* wsum, float* acc, const float* g, float floor, int C, int D, int H, int W, int rd, int rh, int rw,
+                                      int z0, int y0, int x0, int mask, float weight, void* stream) {
+    VX_REQUIRE(mask >= 0 && mask <= 7, "vx_sw_blend_accumulate: mirror mask %d outside 0..7", mask);
+    VxWin P{C, D, H, W, rd, rh, rw, z0, y0, x0};
+    if (int e = vx_win_check(P, "vx_sw_blend_accumulate")) return e;
+    VX_REQUIRE(pred && acc && g, "vx_sw_blend_accumulate: null pointer");
+    VX_REQUIRE(floor > 0.f, "vx_sw_blend_accumulate: the floor of the weights must be positive");
+    VX_REQUIRE((long)rh * rw <= (1L << 30) && (long)C * rd <= (1L << 30), "vx_sw_blend_accumulate: a window of %d x %d planes of %d x %d is beyond the 32-bit plane index", C, rd, rh, rw);
+    const bool v4 = rw % 4 == 0 && W % 4 == 0 && x0 % 4 == 0 && vx_al16(pred) && vx_al16(wsum) && vx_al16(acc);      // (a null wsum counts as aligned)
+    const dim3 grid = vx_plane_grid((long)rh * (rw / (v4 ? 4 : 1)), (long)C * rd);
+    hipStream_t s = (hipStream_t)stream;
+    if (v4 && wsum) vx_sw_blend_accumulate_k<4, true><<<grid, dim3(256), 0, s>>>(pred, wsum, acc, g, floor, P, mask, weight);
+    else if (v4) vx_sw_blend_accumulate_k<4, false><<<grid, dim3(256), 0, s>>>(pred, wsum, acc, g, floor, P, mask, weight);
+    else if (wsum) vx_sw_blend_accumulate_k<1, true><<<grid, dim3(256), 0, s>>>(pred, wsum, acc, g, floor, P, mask, weight);
+    else vx_sw_blend_accumulate_k<1, false><<<grid, dim3(256), 0, s>>>(pred, wsum, acc, g, floor, P, mask, weight);
+    VX_LAUNCH_CHECK("vx_sw_blend_accumulate");
+    return 0;
+}
+
+extern "C" int vx_sw_blend_finalize(const float* acc, float* out, unsigned char* labels, const float* gc, float floor, const int* tab, int cz, int cy, int cx,
+                                    int C, int D, int H, int W, void* stream) {
+    VX_REQUIRE(acc && gc && tab && (out || labels), "vx_sw_blend_finalize: null pointer");
+    VX_REQUIRE(C > 0 && C <= 256 && D > 0 && H > 0 && W > 0 && (long)H * W <= (1L << 30), "vx_sw_blend_finalize: bad shape");
+    VX_REQUIRE(cz > 0 && cy > 0 && cx > 0 && cz <= D && cy <= H && cx <= W, "vx_sw_blend_finalize: covering-window counts (%d,%d,%d) outside 1..(%d,%d,%d)", cz, cy, cx, D, H, W);
+    VX_REQUIRE(floor > 0.f, "vx_sw_blend_finalize: the floor of the weights must be positive");
+    VxBlendGeom P{C, D, H, W, cz, cy, cx};
+    vx_sw_blend_finalize_k<<<vx_plane_grid((long)H * W, D), dim3(256), 0, (hipStream_t)stream>>>(acc, out, labels, gc, floor, tab, P);
+    VX_LAUNCH_CHECK("vx_sw_blend_finalize");
     return 0;
 }
 

@@ -4,12 +4,15 @@
 (utils/inference_runtime.py:4-19); the MONAI call underneath it (monai.inferers.sliding_window_inference, constant blending,
 constant padding) is re-implemented natively: window origins on the host, window extraction / blending / normalisation / argmax in
 HIP kernels (csrc/infer.hip), the predictor being the HIP VeloxSeg forward.  Semantics restated in oracle/sliding_window_oracle.py.
+Beyond the reference's call: mirror test-time augmentation (mirror_axes) and Gaussian importance blending (blend="gaussian", MONAI's
+mode="gaussian"; restated in tests/blend_ref.py).
 """
 from __future__ import annotations
 
 import ctypes
 import itertools
 import math
+import numbers
 import os
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -54,6 +57,78 @@ def _axis_counts(starts_axis: Sequence[int], r: int, m: int, device) -> torch.Te
     for s in starts_axis:
         c[s:s + r] += 1.0
     return c.to(device)
+
+
+BLEND_MODES = ("constant", "gaussian")
+
+
+def _check_blend(blend, sigma_scale) -> Tuple[str, Tuple[float, float, float]]:
+    """-> (blend, one sigma_scale per spatial axis); ValueError on an unknown blend or a sigma_scale that is not one or three positive finite numbers"""
+    if not isinstance(blend, str) or blend not in BLEND_MODES:
+        raise ValueError(f"blend: one of {BLEND_MODES} expected, got {blend!r}")
+    s = list(sigma_scale) if isinstance(sigma_scale, (list, tuple)) else [sigma_scale] * 3
+    if len(s) != 3 or any(isinstance(v, bool) or not isinstance(v, numbers.Real) or not (0.0 < float(v) < math.inf) for v in s):
+        raise ValueError(f"sigma_scale: one or three positive finite numbers expected, got {sigma_scale!r}")
+    return blend, tuple(float(v) for v in s)
+
+
+def gaussian_axis_table(r: int, sigma_scale: float) -> torch.Tensor:
+    """the Gaussian of one window axis, r fp32 values on the host (monai `compute_importance_map`, mode "gaussian", per axis): sigma = r * sigma_scale"""
+    x = torch.arange(-(r - 1) / 2.0, (r - 1) / 2.0 + 1, dtype=torch.float32)
+    return torch.exp(x ** 2 / (-2 * (r * sigma_scale) ** 2))
+
+
+def gaussian_tables(roi: Sequence[int], sigma_scale: Sequence[float]) -> Tuple[List[torch.Tensor], float]:
+    """-> (the three axis tables, floor).  The weight of a window voxel is max((g0[z] * g1[y]) * g2[x], floor), floor = max(smallest unclamped weight, 1e-3) in fp32;
+    the tables are positive and symmetric and rounded multiplication is monotone, so the smallest weight is the corner's."""
+    g = [gaussian_axis_table(int(r), float(s)) for r, s in zip(roi, sigma_scale)]
+    corner = (g[0][0] * g[1][0]) * g[2][0]
+    return g, float(torch.tensor(max(float(corner), 1e-3), dtype=torch.float32))
+
+
+def _cover_tables(starts_axis: Sequence[int], g: torch.Tensor, m: int) -> Tuple[List[int], torch.Tensor]:
+    """one axis of the normaliser's geometry: for every coordinate c < m the number of windows [s, s + len(g)) that cover it, and a (m, largest count) table whose row c
+    holds g[c - s] of those windows in ascending start (the rest of a row is 0 and never read)"""
+    r = int(g.numel())
+    cover = [[c - s for s in starts_axis if s <= c < s + r] for c in range(m)]
+    stride = max(len(row) for row in cover)
+    idx = torch.tensor([row + [0] * (stride - len(row)) for row in cover], dtype=torch.long)
+    keep = torch.tensor([[1.0] * len(row) + [0.0] * (stride - len(row)) for row in cover], dtype=torch.float32)
+    return [len(row) for row in cover], g[idx] * keep
+
+
+class _Blend:
+    """what the Gaussian blending of one volume geometry hands to the kernels: the axis tables (g) for the accumulation, the per-coordinate covering counts (tab) and
+    covering table values (gc) for the normaliser, all on the device, and the floor"""
+
+    def __init__(self, starts, roi, image_size, sigma_scale, device):
+        g, self.floor = gaussian_tables(roi, sigma_scale)
+        self.g = torch.cat(g).to(device)
+        per_axis = [_cover_tables(sorted({s[a] for s in starts}), g[a], image_size[a]) for a in range(3)]
+        self.strides = tuple(int(t.shape[1]) for _, t in per_axis)
+        self.tab = torch.tensor([n for counts, _ in per_axis for n in counts], dtype=torch.int32).to(device)
+        self.gc = torch.cat([t.reshape(-1) for _, t in per_axis]).to(device)
+
+
+_BLENDS = {}          # the last few geometries' tables: a few KB each, read-only once uploaded (a volume series shares one geometry)
+
+
+def _blend_tables(starts, roi, image_size, sigma_scale, device) -> _Blend:
+    key = (tuple(roi), tuple(image_size), tuple(sigma_scale), tuple(starts[0]), tuple(starts[-1]), len(starts), str(device))
+    hit = _BLENDS.get(key)
+    if hit is None or hit[0] != starts:
+        if len(_BLENDS) >= 8:
+            _BLENDS.pop(next(iter(_BLENDS)))
+        hit = _BLENDS[key] = (list(starts), _Blend(starts, roi, image_size, sigma_scale, device))
+    return hit[1]
+
+
+def _accumulate(prob_k, acc_b, K, dhw, roi, origin, blend, stream):
+    """one window into the blending: acc[window] += prob (constant) or += w * prob (Gaussian)"""
+    if blend is None:
+        H.call("vx_sw_accumulate", H.P(prob_k), H.P(acc_b), K, *dhw, *roi, *origin, 1.0, stream)
+    else:
+        H.call("vx_sw_blend_accumulate", H.P(prob_k), None, H.P(acc_b), H.P(blend.g), blend.floor, K, *dhw, *roi, *origin, 0, 1.0, stream)
 
 
 SW_MAX_WINDOWS = 16  # VX_SW_MAX_WINDOWS of include/veloxseg_hip.h: windows per vx_sw_extract_mirror launch (a larger sw_batch_size takes several)
@@ -108,13 +183,17 @@ def _mirrored_forwards(inputs, win, idxs, starts, num_win, geom, masks, run, wsu
     return wsum, None
 
 
-def _accumulate_mirrored(prob, wsum, acc, idxs, starts, num_win, geom, mask, weight, stream):
-    """acc[window] += weight * (wsum + flip_mask(prob)), one launch per window in window order"""
+def _accumulate_mirrored(prob, wsum, acc, idxs, starts, num_win, geom, mask, weight, stream, blend=None):
+    """acc[window] += weight * (wsum + flip_mask(prob)), one launch per window in window order; blend (Gaussian): += w * (weight * (wsum + flip_mask(prob)))"""
     D, Hh, W, rd, rh, rw = geom[2:]
     K = int(prob.shape[1])
     for k, i in enumerate(idxs):
         z0, y0, x0 = starts[i % num_win]
-        H.call("vx_sw_mirror_accumulate", H.P(prob[k]), H.P(wsum[k]), H.P(acc[i // num_win]), K, D, Hh, W, rd, rh, rw, z0, y0, x0, mask, weight, stream)
+        if blend is None:
+            H.call("vx_sw_mirror_accumulate", H.P(prob[k]), H.P(wsum[k]), H.P(acc[i // num_win]), K, D, Hh, W, rd, rh, rw, z0, y0, x0, mask, weight, stream)
+        else:
+            H.call("vx_sw_blend_accumulate", H.P(prob[k]), H.P(wsum[k]), H.P(acc[i // num_win]), H.P(blend.g), blend.floor, K, D, Hh, W, rd, rh, rw, z0, y0, x0,
+                   mask, weight, stream)
 
 
 # two window batches in flight (round 6): each forward of a window batch is a ~250-launch tape that leaves most of the chip idle at the reference's sw_batch_size of 2; the next
@@ -124,7 +203,7 @@ SW_PIPELINE = True
 SW_INFLIGHT = 2      # window batches in flight
 
 
-def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi):
+def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi, blend=None):
     C, D, Hh, W = cdhw
     rd, rh, rw = roi
     dev = inputs.device
@@ -145,8 +224,7 @@ def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi):
     B = inputs.shape[0]
     acc = torch.zeros((B, K, D, Hh, W), device=dev, dtype=torch.float32)
     for k in range(swb):
-        z0, y0, x0 = starts[k % num_win]
-        H.call("vx_sw_accumulate", H.P(prob[k]), H.P(acc[k // num_win]), K, D, Hh, W, rd, rh, rw, z0, y0, x0, 1.0, H.stream_ptr())
+        _accumulate(prob[k], acc[k // num_win], K, (D, Hh, W), roi, starts[k % num_win], blend, H.stream_ptr())
     # the rest alternately on the two slot streams
     for s_ in streams:
         s_.wait_stream(cur)
@@ -172,8 +250,7 @@ def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi):
                 st_.wait_event(last_acc)                     # blending in window order: bit for bit the sequential sums
             for k in range(swb):
                 i = bi * swb + k
-                z0, y0, x0 = starts[i % num_win]
-                H.call("vx_sw_accumulate", H.P(out[k]), H.P(acc[i // num_win]), K, D, Hh, W, rd, rh, rw, z0, y0, x0, 1.0, st_.cuda_stream)
+                _accumulate(out[k], acc[i // num_win], K, (D, Hh, W), roi, starts[i % num_win], blend, st_.cuda_stream)
             last_acc = torch.cuda.Event()
             last_acc.record(st_)
     for s_ in streams:
@@ -181,7 +258,7 @@ def _pipelined(inputs, predictor, starts, num_win, total, swb, cdhw, roi):
     return acc, K
 
 
-def _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks):
+def _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks, blend=None):
     """_pipelined with mirror test-time augmentation: the len(masks) forwards of a window batch run one after the other on that batch's slot (its tape replica, its
     stream); two batches stay in flight, their forwards issued in turn, and the blending of batch i + 1 waits for the one of batch i, so the sums are those of the
     sequential loop bit for bit."""
@@ -227,7 +304,7 @@ def _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, ma
             with torch.cuda.stream(st_):
                 if last_acc is not None:
                     st_.wait_event(last_acc)                 # blending in window order
-                _accumulate_mirrored(last[bi], wsums[bi % SW_INFLIGHT], acc, idxs_of(bi), starts, num_win, geom, masks[-1], weight, st_.cuda_stream)
+                _accumulate_mirrored(last[bi], wsums[bi % SW_INFLIGHT], acc, idxs_of(bi), starts, num_win, geom, masks[-1], weight, st_.cuda_stream, blend)
                 last_acc = torch.cuda.Event()
                 last_acc.record(st_)
     for s_ in streams:
@@ -235,11 +312,11 @@ def _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, ma
     return acc, K
 
 
-def _run_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks):
+def _run_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks, blend=None):
     """mirror test-time augmentation: len(masks) forwards per window batch, summed window by window -> (acc, K).  Pipelined under the plain driver's conditions
     (a predictor with tape replicas, at least two full window batches, no ragged one), else one batch after the other on the caller's stream."""
     if SW_PIPELINE and hasattr(predictor, "forward_slot") and total >= 2 * swb and total % swb == 0:
-        return _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks)
+        return _pipelined_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks, blend)
     B, C, D, Hh, W, rd, rh, rw = geom
     acc = win = wsum = None
     for g in range(0, total, swb):
@@ -249,7 +326,7 @@ def _run_mirrored(inputs, predictor, starts, num_win, total, swb, geom, masks):
         wsum, prob = _mirrored_forwards(inputs, win[:len(idxs)], idxs, starts, num_win, geom, masks, predictor, wsum, H.stream_ptr())
         if acc is None:
             acc = torch.zeros((B, int(prob.shape[1]), D, Hh, W), device=inputs.device, dtype=torch.float32)
-        _accumulate_mirrored(prob, wsum, acc, idxs, starts, num_win, geom, masks[-1], 1.0 / len(masks), H.stream_ptr())
+        _accumulate_mirrored(prob, wsum, acc, idxs, starts, num_win, geom, masks[-1], 1.0 / len(masks), H.stream_ptr(), blend)
     return acc, int(acc.shape[1])
 
 
@@ -258,18 +335,26 @@ _SW_STREAMS = {}
 
 def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, predictor: Callable, overlap: float = 0.25,
                              mode: str = "constant", padding_mode: str = "constant", cval: float = 0.0, return_labels: bool = False,
-                             mirror_axes: Sequence[int] = (), sw_device=None, device=None, **unsupported):
+                             mirror_axes: Sequence[int] = (), sw_device=None, device=None, blend: str = "constant", sigma_scale=0.125, **unsupported):
     """-> blended predictions (B, K, D, H, W) fp32, or (predictions, uint8 argmax labels (B, 1, D, H, W)) with return_labels.
     Only the arguments the reference drivers use are supported (constant blending / padding); anything else raises.
     mirror_axes: mirror test-time augmentation over these spatial axes (0 = D, 1 = H, 2 = W): every window is also predicted under each mirror of
     mirror_schedule(mirror_axes), the predictions are mirrored back and summed window by window in schedule order, and the window enters the blending with weight
     1 / n -- bit for bit the result of the plain call on the predictor that averages its mirrored predictions.  () = off.
+    blend: "constant" (every window counts the same; the default, and with it every launch is the one of the call without the keyword) or "gaussian": every window is
+    weighted by a Gaussian importance map, w = max((g_0[z] * g_1[y]) * g_2[x], floor) with g_a = exp(-x^2 / (2 (r_a * sigma_scale_a)^2)) over the window axis a and
+    floor = max(smallest such product, 1e-3), and the sum is divided by the sum of the weights of the covering windows, added in window order.
+    blend="gaussian" is MONAI's mode="gaussian" (restated from MONAI 1.5, not pinned against MONAI itself: it forms its map on sw_device, here the axis tables are formed
+    on the host); `mode` keeps its contract -- "constant" only, anything else raises NotImplementedError -- and aliasing it is left to a later change.
+    sigma_scale: one positive number or one per spatial axis (used by blend="gaussian").  An unknown blend or a bad sigma_scale raises ValueError before any GPU work.
+    With mirror_axes the window enters as w * ((1 / n) * sum of its mirrored-back predictions): the plain Gaussian call on the mirror-averaging predictor.
     sw_device: where the windows are predicted -- None or the inputs' device (there is no other path).  device: where the RESULT lives (the reference's huge-volume
     call passes "cpu"); the blending itself stays on the GPU and the result is moved once at the end."""
     if str(mode).lower() not in ("constant", "blendmode.constant") or str(padding_mode).lower() not in ("constant", "pytorchpadmode.constant"):
         raise NotImplementedError("veloxseg_amd sliding window: constant blending / constant padding only (what utils/inference_*.py use)")
     if unsupported:
         raise NotImplementedError(f"veloxseg_amd sliding window: unsupported arguments {sorted(unsupported)}")
+    blend, sigma_scale = _check_blend(blend, sigma_scale)
     if inputs.dim() != 5:
         raise ValueError("sliding window expects (B, C, D, H, W)")
     if not inputs.is_cuda:
@@ -299,18 +384,20 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_b
     rd, rh, rw = patch
     dev = inputs.device
     st = H.stream_ptr
-    cz = _axis_counts(sorted({s[0] for s in starts}), rd, D, dev)
-    cy = _axis_counts(sorted({s[1] for s in starts}), rh, Hh, dev)
-    cx = _axis_counts(sorted({s[2] for s in starts}), rw, W, dev)
+    gauss = _blend_tables(starts, patch, image_size, sigma_scale, dev) if blend == "gaussian" else None
+    if gauss is None:
+        cz = _axis_counts(sorted({s[0] for s in starts}), rd, D, dev)
+        cy = _axis_counts(sorted({s[1] for s in starts}), rh, Hh, dev)
+        cx = _axis_counts(sorted({s[2] for s in starts}), rw, W, dev)
     num_win = len(starts)
     total = num_win * B
     acc = None
     K = None
     if len(masks) > 1:
-        acc, K = _run_mirrored(inputs, predictor, starts, num_win, total, sw_batch_size, (B, C, D, Hh, W, rd, rh, rw), masks)
+        acc, K = _run_mirrored(inputs, predictor, starts, num_win, total, sw_batch_size, (B, C, D, Hh, W, rd, rh, rw), masks, gauss)
         total = 0                                           # (the plain path below has nothing left)
     if (SW_PIPELINE and hasattr(predictor, "forward_slot") and total >= 2 * sw_batch_size and total % sw_batch_size == 0):
-        done = _pipelined(inputs, predictor, starts, num_win, total, sw_batch_size, (C, D, Hh, W), (rd, rh, rw))
+        done = _pipelined(inputs, predictor, starts, num_win, total, sw_batch_size, (C, D, Hh, W), (rd, rh, rw), gauss)
         if done is not None:
             acc, K = done
             total = 0                                       # (every window batch is in; the loop below has nothing left)
@@ -330,12 +417,15 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_b
                 raise NotImplementedError("predictor output must have the window's spatial size")
             acc = torch.zeros((B, K, D, Hh, W), device=dev, dtype=torch.float32)
         for k, i in enumerate(idxs):
-            z0, y0, x0 = starts[i % num_win]
-            H.call("vx_sw_accumulate", H.P(prob[k]), H.P(acc[i // num_win]), K, D, Hh, W, rd, rh, rw, z0, y0, x0, 1.0, st())
+            _accumulate(prob[k], acc[i // num_win], K, (D, Hh, W), patch, starts[i % num_win], gauss, st())
     labels = torch.empty((B, 1, D, Hh, W), device=dev, dtype=torch.uint8) if return_labels else None
     for b in range(B):
-        H.call("vx_sw_finalize", H.P(acc[b]), H.P(acc[b]), H.P(labels[b], torch.uint8) if return_labels else None, H.P(cz), H.P(cy), H.P(cx),
-               K, D, Hh, W, st())
+        if gauss is None:
+            H.call("vx_sw_finalize", H.P(acc[b]), H.P(acc[b]), H.P(labels[b], torch.uint8) if return_labels else None, H.P(cz), H.P(cy), H.P(cx),
+                   K, D, Hh, W, st())
+        else:
+            H.call("vx_sw_blend_finalize", H.P(acc[b]), H.P(acc[b]), H.P(labels[b], torch.uint8) if return_labels else None, H.P(gauss.gc), gauss.floor,
+                   H.P(gauss.tab, torch.int32), *gauss.strides, K, D, Hh, W, st())
     if any(pad):
         lo = [pad[4], pad[2], pad[0]]
         crop = (slice(None), slice(None)) + tuple(slice(l, l + m) for l, m in zip(lo, image_size_))
@@ -349,7 +439,11 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Sequence[int], sw_b
 
 def sliding_window_predict(inputs, predictor, roi_size, sw_batch_size, test_config, **kwargs):
     """reference signature (utils/inference_runtime.py:4-19): overlap comes from test_config["sliding_window"]["overlap"], and so does mirror_axes
-    (test_config["sliding_window"]["mirror_axes"], optional) unless the keyword is given"""
+    (test_config["sliding_window"]["mirror_axes"], optional) unless the keyword is given; likewise blend and sigma_scale (test_config["sliding_window"]["blend"],
+    ["sigma_scale"], both optional)"""
+    for key in ("blend", "sigma_scale"):
+        if key not in kwargs and test_config["sliding_window"].get(key) is not None:
+            kwargs[key] = test_config["sliding_window"][key]
     if "mirror_axes" not in kwargs and test_config["sliding_window"].get("mirror_axes") is not None:
         kwargs["mirror_axes"] = tuple(test_config["sliding_window"]["mirror_axes"])
     return sliding_window_inference(inputs, roi_size, sw_batch_size, predictor=predictor, overlap=test_config["sliding_window"]["overlap"], **kwargs)
@@ -369,7 +463,7 @@ class Net(torch.nn.Module):
 
 @torch.inference_mode()
 def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, overlap: float, taped: bool = True, postprocess=None,
-                 mirror_axes: Sequence[int] = ()):
+                 mirror_axes: Sequence[int] = (), blend: str = "constant", sigma_scale=0.125):
     """eval-mode sliding-window segmentation of one (B, C, D, H, W) volume -> (blended logits, uint8 label map).
     postprocess (a utils.components.Postprocess, or the dict its from_config takes): the returned label map is the cleaned-up one (components below a voxel
     count dropped / the k largest kept, on the GPU); the returned logits are untouched.
@@ -378,7 +472,8 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
     overwrites it (same stream).  The predictor hangs on the model object (no process-wide cache, nothing outlives the model) and re-captures
     when the parameters / buffers were re-homed since the capture (TrainEngine's flat buffer, .to(), a parameter swap): a tape bakes in raw
     device pointers.
-    mirror_axes: mirror test-time augmentation (sliding_window_inference); mirrored windows have the window's shape and replay the same tape and replicas."""
+    mirror_axes: mirror test-time augmentation (sliding_window_inference); mirrored windows have the window's shape and replay the same tape and replicas.
+    blend, sigma_scale: constant or Gaussian importance blending (sliding_window_inference); the forwards, their tapes and replicas are the same for both."""
     was_training = model.training
     model.eval()
     try:
@@ -391,7 +486,8 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
             if pred is None:
                 pred = TapedPredictor(net)
                 model.__dict__["_vx_taped_predictor"] = pred       # plain attribute (not a sub-module): dies with the model
-        logits, labels = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True, mirror_axes=mirror_axes)
+        logits, labels = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True, mirror_axes=mirror_axes, blend=blend,
+                                                  sigma_scale=sigma_scale)
         if postprocess is not None:
             from .components import Postprocess
             labels = (postprocess if isinstance(postprocess, Postprocess) else Postprocess.from_config(postprocess))(labels)
