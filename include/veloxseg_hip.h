@@ -600,6 +600,32 @@ int vx_label_kth_in_chunk(const void* labels, int lab_bytes, long n, long chunk_
  * (round half to even); out must not alias x; cos_a and sin_a are taken as given (they need not form a rotation) */
 int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float cos_a, float sin_a, int mode, void* stream);
 
+/* ---- training batch assembly (csrc/augment_batch.hip): mirror, intensity steps and noise, written straight into the batch ----
+ * `records` is a DEVICE table of n_image + n_label records of VX_AUG_RECORD_BYTES bytes, the image records first; one record = one channel of one source:
+ *   byte   0  uint64  source device pointer (any alignment of its element type)
+ *   byte   8  int64   strides of the source over (D, H, W), in elements, >= 0 (crop views of a larger volume are fine)
+ *   byte  32  int32   element type: 0 = fp32 image, or a label code 1 = uint8, 4 = int32, 8 = int64, -4 = float32
+ *   byte  36  int32   b: destination sample, 0 <= b < B
+ *   byte  40  int32   c: destination channel, 0 <= c < M (image) or VX_AUG_LABEL = -1 (label)
+ *   byte  44  int32   flip mask, bit a = axis a of (D, H, W) mirrored: out[d, h, w] = src[D-1-d | d, H-1-h | h, W-1-w | w]
+ *   byte  48  int32   number of pointwise steps, 0..VX_AUG_MAX_STEPS (images only); bytes 52..63 unused
+ *   byte  64  8 steps of 16 bytes { uint32 op, float a, float b, uint32 key }, applied in order, each operation rounded to fp32 on its own (nothing is contracted):
+ *               op & 15 = 1  mul    t = t * a
+ *               op & 15 = 2  add    t = t + a
+ *               op & 15 = 3  noise  t = t + (a + b * n),  n = the standard normal of (key, e), e = cn * D*H*W + flat index of the voxel in the patch, cn = op >> 8;
+ *                                   (op >> 4) & 7 is the mask of the flips that FOLLOW the noise step: the voxel index is taken under that mirror (0: the output voxel)
+ *             n: Philox4x32-7 words r[0..3] of (key, stream VX_AUG_NOISE_STREAM, counter e >> 2); elements 4k, 4k+1 use (r[0], r[1]), elements 4k+2, 4k+3 use (r[2], r[3]):
+ *             u1 = ((ra >> 8) + 1) * 2^-24 in (0, 1], u2 = (rb >> 8) * 2^-24, rad = sqrt(-2 ln u1); the even element gets rad * cos(2 pi u2), the odd one rad * sin(2 pi u2).
+ * Images go to x_out (B, M, D, H, W) fp32, labels to y_out (B, 1, D, H, W) int64 with the value a C cast gives (float32 truncates, integers widen); label_bytes is
+ * the width of y_out's elements and must be 8.  Both outputs 16-byte aligned; x_out may be NULL when n_image = 0, y_out when n_label = 0.  At most two launches (images,
+ * labels), none per record.  A record whose type, b or c is out of range writes nothing.  Checked before any launch (-1, outputs untouched): pointers, positive
+ * shapes, n_image + n_label > 0, label_bytes = 8, 1 <= M <= 64. */
+#define VX_AUG_RECORD_BYTES 192
+#define VX_AUG_MAX_STEPS 8
+#define VX_AUG_LABEL (-1)
+#define VX_AUG_NOISE_STREAM 0x564158475541ull      /* "AUGXAV": far above every dropout site id (those count up from 1, functional.new_dropout_site) */
+int vx_augment_batch(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream);
+
 /* ---- volume preprocessing (csrc/preprocess.hip): foreground z-score, CT clip + normalise, dataset order statistics, separable resampling -----------------
  * Reference: preprocess/normalization_MRI.py:7-12,52, preprocess/normalization_CT_PET.py:6-11,23-31,65-81, utils/inference_extern_mri.py:73-75,95.
  * Volumes are fp32 contiguous, indexed with `long`; masks / labels are uint8 / int32 / int64 / fp32 (bytes code 1 / 4 / 8 / -4, as in vx_label_chunk_count),

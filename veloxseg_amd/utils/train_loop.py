@@ -51,9 +51,11 @@ class SyntheticPatches:
 
 class SyntheticVolumes:
     """whole synthetic cases (padded background + a foreground body + lesion blobs) pushed through the reference's transform chain on the GPU
-    (utils/augment.py: CropForegroundd -> RandCropByPosNegLabeld(num_samples) -> RandRotated): `batch` patches per step, batch / num_samples cases per step"""
+    (utils/augment.py: CropForegroundd -> RandCropByPosNegLabeld(num_samples) -> RandRotated): `batch` patches per step, batch / num_samples cases per step.
+    augment: None (the chain above, batches put together with cat / stack / .long()) or the train_config["augment"] dict of utils.augment.from_config: mirror, scale,
+    shift and noise drawn per patch and applied while ONE kernel call writes the batch (utils.augment.BatchAssembler)"""
 
-    def __init__(self, model_cfg, batch, steps, device, volume=(160, 160, 144), num_samples=2, seed=12345, rotate_degrees=15.0):
+    def __init__(self, model_cfg, batch, steps, device, volume=(160, 160, 144), num_samples=2, seed=12345, rotate_degrees=15.0, augment=None):
         from . import augment as A
         if batch % num_samples:
             raise ValueError("batch must be a multiple of num_samples")
@@ -65,6 +67,8 @@ class SyntheticVolumes:
             A.RandCropByPosNegLabeld(self.keys, "seg", model_cfg["input_size"], pos=1, neg=1, num_samples=num_samples),
             A.RandRotated(self.keys, range_z=A.rotation_range_from_degrees(rotate_degrees), mode=A.image_label_modes(self.M), prob=0.5),
         ]).set_random_state(seed)
+        # its own seed sequence: the assembler's transforms must not repeat the streams of the chain above
+        self.assembler = None if augment is None else A.from_config(augment, self.keys[:-1], "seg").set_random_state([int(seed) & 0xFFFFFFFF, 0xA6])
 
     def __len__(self):
         return self.steps
@@ -90,6 +94,9 @@ class SyntheticVolumes:
     def __iter__(self):
         g = torch.Generator(device=self.device).manual_seed(self.seed)
         for _ in range(self.steps):
+            if self.assembler is not None:
+                yield self.assembler([d for _ in range(self.batch // self.ns) for d in self.pipe(self.case(g))])
+                continue
             xs, ys = [], []
             for _ in range(self.batch // self.ns):
                 for d in self.pipe(self.case(g)):
@@ -131,8 +138,11 @@ def run_train(args, train_config, model_config, train_loader: Optional[Iterable]
     rank = dist.get_rank() if ddp else 0
     if train_loader is None:
         # every rank draws its OWN synthetic stream (seed + rank): data parallelism must add data, not replicate the same batch on every GPU
-        source = SyntheticVolumes if getattr(args, "augment", False) else SyntheticPatches
-        train_loader = source(mcfg, batch, getattr(args, "synthetic_steps", 4), device, seed=12345 + rank)
+        # --augment with train_config["augment"] set: mirror / intensity / noise on top of the chain (utils.augment.from_config); without the key, the chain alone
+        if getattr(args, "augment", False):
+            train_loader = SyntheticVolumes(mcfg, batch, getattr(args, "synthetic_steps", 4), device, seed=12345 + rank, augment=train_config.get("augment"))
+        else:
+            train_loader = SyntheticPatches(mcfg, batch, getattr(args, "synthetic_steps", 4), device, seed=12345 + rank)
     # engine buffers from the configuration, not from a pulled batch (that would consume one batch of a one-shot iterable and spin up an extra
     # worker pool); loaders must yield (batch_size, sum(in_ch), *input_size) inputs -- labels of any integer dtype are converted by the copy
     size = list(mcfg["input_size"])
