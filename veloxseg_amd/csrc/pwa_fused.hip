@@ -28,8 +28,131 @@ template <int T> struct Geo { static constexpr int NT = 16 * T; static constexpr
 // out rows [16 mt, 16 mt + 16) for the row tiles of this wave.  W(m, k) = w[m * wsm + k * wsk]; TR = (wsk != 1).  Up to 3 K-segments with their own
 // weight pointers (concatenated reduction axis: the three projections of the pre-backward).  `in` = LDS act[K total][S].  epi(mt, acc):
 // acc[j][reg] = out[16 mt + 4 q + reg][voxel (T == 4 ? 4 r + j : r)]
+//
+// The A operand runs one chunk (KP pieces of 16 k: 64 k, or 16 k for the K = 16 products of the 32^3 level) AHEAD of the matrix pipe over the wave's whole work
+// list -- (row tile, segment, chunk) flattened, so the first chunk of the next row tile or segment is in flight under this one's MFMAs and epilogue -- and across
+// the stages of a chain: `pre` holds the wave's FIRST chunk, which the caller requests with tile_gemm_first at the top of the kernel or before the barrier that
+// closes the previous stage.  Weights depend on nothing a kernel computes, and vx_bar() does not wait for global loads.  Every output element is still ONE
+// accumulator chain over k in ascending order.
+// The request inside the loop is unconditional and the last chunk is peeled off: a fixed number of loads in flight at the MFMAs lets the compiler wait for exactly
+// the chunk it needs (vmcnt(n)); a request under a condition made it wait for everything, the prefetch included.
+//
+// Sharing: wave-slot wl of WG takes row tiles wl, wl + WG, ...; NJ < T (T = 4 only) = this wave owns n-tiles [j0, j0 + NJ) of the four interleaved ones, so a
+// product with fewer row tiles than waves still occupies every wave.  epi(mt, acc): acc[jj][reg] = out[16 mt + 4 q + reg][voxel (T == 4 ? 4 r + j0 + jj : r)]
+typedef const __attribute__((address_space(1))) float* gcf;
+typedef const __attribute__((address_space(1))) vx_f32x4* gcf4;
+struct AFrag { float a[4][4]; };
+
+// LDS-only barrier: the stages of these chains hand data to each other through LDS alone (no thread reads global memory another thread of the block wrote), so the
+// barrier orders LDS and leaves global loads and stores in flight -- __syncthreads() waits for every outstanding global access of the wave, weight prefetch included
+__device__ __forceinline__ void vx_bar() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// one chunk of the lane's weight row: k = k0 + 16 c + 4 q + i, c < KP.  K % 16 == 0 (the *_ok gates); pieces beyond K reload the last one (clamped, never used)
+// (the pointer is cast to GLOBAL: a FLAT load is slower and is counted on the LDS wait counter as well, so that every wait for a B operand would also wait for the prefetch)
+template <bool TR, int KP>
+__device__ __forceinline__ void load_a(float (&dst)[4][4], const float* __restrict__ wrow_, int K, int k0, int wsk) {
+    const int q = (threadIdx.x & 63) >> 4;
+    gcf wrow = (gcf)(unsigned long long)wrow_;
+#pragma unroll
+    for (int c = 0; c < KP; ++c) {
+        const int kb = min(k0 + 16 * c, K - 16) + 4 * q;
+        if (!TR) {
+            const vx_f32x4 t = *(gcf4)(wrow + kb);
+            dst[c][0] = t[0]; dst[c][1] = t[1]; dst[c][2] = t[2]; dst[c][3] = t[3];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dst[c][i] = wrow[(long)(kb + i) * wsk];
+        }
+    }
+}
+// the first chunk of a product for wave-slot wl (nothing when the slot has no row tile); wrow(mt, sg) = this lane's row of W: &W(16 mt + r, 0) of segment sg
+template <bool TR, int KP, class WRow>
+__device__ __forceinline__ void tile_gemm_first(AFrag& f, int wl, int K0, int wsk, int Mrows, WRow&& wrow) {
+    if (wl * 16 < Mrows) load_a<TR, KP>(f.a, wrow(wl, 0), K0, 0, wsk);
+}
+
+template <int T, int NJ, bool TR, int KP, class WRow, class Epi>
+__device__ __forceinline__ void tile_gemm(AFrag& pre, int wl, int WG, int j0, int nseg, int K0, int K1, int K2, int wsk, int Mrows, WRow&& wrow, const float* __restrict__ in,
+                                          Epi&& epi) {
+    constexpr int S = Geo<T>::S, KC = 16 * KP;
+    static_assert(NJ == T || (T == 4 && (NJ == 1 || NJ == 2)), "n-tile sharing: T = 4 only");
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    if (wl * 16 >= Mrows) return;
+    float (&a)[4][4] = pre.a;
+    auto Kof = [&](int s) { return s == 0 ? K0 : (s == 1 ? K1 : K2); };        // (selects, not an indexed array: no scratch)
+    float an[4][4];
+    vx_f32x4 acc[NJ];
+    auto chunk = [&](int K, int k0, int kin) {
+        if (kin == 0 && k0 == 0) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[j] = (vx_f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            if (k0 + 16 * c < K) {                    // wave-uniform
+                const float* __restrict__ brow = in + (long)(kin + k0 + 16 * c + 4 * q) * S;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if constexpr (T == 4 && NJ == 4) {
+                        const float4 bv = *reinterpret_cast<const float4*>(brow + i * S + 4 * r);
+                        acc[0] = VX_MFMA(a[c][i], bv.x, acc[0]);
+                        acc[1] = VX_MFMA(a[c][i], bv.y, acc[1]);
+                        acc[2] = VX_MFMA(a[c][i], bv.z, acc[2]);
+                        acc[3] = VX_MFMA(a[c][i], bv.w, acc[3]);
+                    } else if constexpr (T == 4 && NJ == 2) {
+                        const float2 bv = *reinterpret_cast<const float2*>(brow + i * S + 4 * r + j0);
+                        acc[0] = VX_MFMA(a[c][i], bv.x, acc[0]);
+                        acc[1] = VX_MFMA(a[c][i], bv.y, acc[1]);
+                    } else if constexpr (T == 4) {
+                        acc[0] = VX_MFMA(a[c][i], brow[i * S + 4 * r + j0], acc[0]);
+                    } else {
+                        acc[0] = VX_MFMA(a[c][i], brow[i * S + r], acc[0]);
+                    }
+                }
+            }
+        }
+    };
+    int mt = wl, sg = 0, k0 = 0, kin = 0;
+    for (;;) {
+        const int K = Kof(sg);
+        int nmt = mt, nsg = sg, nk0 = k0 + KC;                                 // the chunk after this one
+        if (nk0 >= K) { nk0 = 0; if (++nsg >= nseg) { nsg = 0; nmt += WG; } }
+        if (nmt * 16 >= Mrows) break;                                          // the wave's last chunk: below
+        load_a<TR, KP>(an, wrow(nmt, nsg), Kof(nsg), nk0, wsk);
+        chunk(K, k0, kin);
+        if (nk0 == 0) {                               // the segment ends here
+            kin += K;
+            if (nsg == 0) { epi(mt, acc); kin = 0; }  // ... and so does the row tile
+        }
+#pragma unroll
+        for (int c = 0; c < KP; ++c)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[c][i] = an[c][i];
+        mt = nmt; sg = nsg; k0 = nk0;
+    }
+    chunk(Kof(sg), k0, kin);
+    epi(mt, acc);
+}
+// one weight matrix, row tiles over the NW waves: W(m, k) = w[m * wsm + k * wsk]
 template <int T, int NW, bool TR, class Epi>
-__device__ __forceinline__ void tile_gemm(int nseg, const float* const (&w)[3], const int (&Kseg)[3], int wsm, int wsk, int Mrows, const float* __restrict__ in, Epi&& epi) {
+__device__ __forceinline__ void tile_gemm1(AFrag& pre, const float* w, int K, int wsm, int wsk, int Mrows, const float* __restrict__ in, Epi&& epi) {
+    const int r = threadIdx.x & 15;
+    tile_gemm<T, T, TR, 4>(pre, threadIdx.x >> 6, NW, 0, 1, K, 0, 0, wsk, Mrows, [&](int mt, int) { return w + (long)(16 * mt + r) * wsm; }, in, epi);
+}
+template <int NW, bool TR>
+__device__ __forceinline__ void tile_gemm1_first(AFrag& f, const float* w, int K, int wsm, int wsk, int Mrows) {
+    const int r = threadIdx.x & 15;
+    tile_gemm_first<TR, 4>(f, threadIdx.x >> 6, K, wsk, Mrows, [&](int mt, int) { return w + (long)(16 * mt + r) * wsm; });
+}
+
+// The chains that measured no faster with the look-ahead above (the T = 1 pre-backward, both post-backward tile widths, the channel-stage backward: DESIGN.md) keep
+// the sequential form: a wave's row tiles one after the other, the A operand one chunk ahead inside a (row tile, segment) only, loaded at its head.
+template <int T, int NW, bool TR, class Epi>
+__device__ __forceinline__ void tile_gemm_seq(int nseg, const float* const (&w)[3], const int (&Kseg)[3], int wsm, int wsk, int Mrows, const float* __restrict__ in, Epi&& epi) {
     constexpr int S = Geo<T>::S;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     for (int mt = wave; mt * 16 < Mrows; mt += NW) {
@@ -94,50 +217,58 @@ __device__ __forceinline__ void tile_gemm(int nseg, const float* const (&w)[3], 
     }
 }
 template <int T, int NW, bool TR, class Epi>
-__device__ __forceinline__ void tile_gemm1(const float* w, int K, int wsm, int wsk, int Mrows, const float* __restrict__ in, Epi&& epi) {
+__device__ __forceinline__ void tile_gemm1_seq(const float* w, int K, int wsm, int wsk, int Mrows, const float* __restrict__ in, Epi&& epi) {
     const float* const ws[3] = {w, nullptr, nullptr};
     const int ks[3] = {K, 0, 0};
-    tile_gemm<T, NW, TR>(1, ws, ks, wsm, wsk, Mrows, in, epi);
+    tile_gemm_seq<T, NW, TR>(1, ws, ks, wsm, wsk, Mrows, in, epi);
 }
 
 // rows [0, R) of a (R, V) slab of one sample into LDS act[row][S]; columns beyond V read as 0.  16 threads per row (float4 each for T = 4).
 // Eight rows per thread are in flight at once: the loads are unconditional (clamped address, value selected afterwards) -- a loop of the form
 // `if (ok) v = src[i]; lds[e] = v;` pays one memory latency per trip (DESIGN.md lesson -1).
-template <int T, int NW>
-__device__ __forceinline__ void load_tile(float* __restrict__ dst, const float* __restrict__ src /* row 0 of the sample */, int R, long V, long v0) {
-    constexpr int S = Geo<T>::S, RP = 4 * NW, U = 8;
+// The two halves are separate so that a caller can put independent work between the request and the LDS store (tile_fetch ... tile_commit).  Rows at or beyond R
+// are not requested: R % 16 == 0, so the test is wave-uniform, and a 16-row tile on a 4-wave block used to ask for its last row seven more times.
+template <int T> struct TileVec { typedef float type; };
+template <> struct TileVec<4> { typedef float4 type; };
+template <int T, int NW, int U>
+__device__ __forceinline__ void tile_fetch(typename TileVec<T>::type (&t)[U], const float* __restrict__ src, int R, long V, long v0, int row0) {
+    constexpr int RP = 4 * NW;
     const int cg = threadIdx.x & 15;
-    for (int row0 = threadIdx.x >> 4; row0 < R; row0 += U * RP) {
-        if constexpr (T == 4) {
-            const long v = v0 + 4 * cg;
-            const bool ok = v < V;
-            const long vc = ok ? v : 0;
-            float4 t[U];
+    const long v = v0 + T * cg;
+    const long vc = v < V ? v : 0;                   // clamped address, the value is selected at the commit
 #pragma unroll
-            for (int u = 0; u < U; ++u) { const int row = min(row0 + u * RP, R - 1); t[u] = *reinterpret_cast<const float4*>(src + (long)row * V + vc); }
+    for (int u = 0; u < U; ++u) {
+        const int row = row0 + u * RP;
+        if (row < R) t[u] = *reinterpret_cast<const typename TileVec<T>::type*>(src + (long)row * V + vc);
+    }
+}
+template <int T, int NW, int U>
+__device__ __forceinline__ void tile_commit(float* __restrict__ dst, const typename TileVec<T>::type (&t)[U], int R, long V, long v0, int row0) {
+    constexpr int S = Geo<T>::S, RP = 4 * NW;
+    const int cg = threadIdx.x & 15;
+    const bool ok = v0 + T * cg < V;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int row = row0 + u * RP;
-                if (row < R) *reinterpret_cast<float4*>(dst + row * S + 4 * cg) = ok ? t[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        } else {
-            const long v = v0 + cg;
-            const bool ok = v < V;
-            const long vc = ok ? v : 0;
-            float t[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) { const int row = min(row0 + u * RP, R - 1); t[u] = src[(long)row * V + vc]; }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int row = row0 + u * RP;
-                if (row < R) dst[row * S + cg] = ok ? t[u] : 0.0f;
-            }
+    for (int u = 0; u < U; ++u) {
+        const int row = row0 + u * RP;
+        if (row < R) {
+            if constexpr (T == 4) *reinterpret_cast<float4*>(dst + row * S + 4 * cg) = ok ? t[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+            else dst[row * S + cg] = ok ? t[u] : 0.0f;
         }
+    }
+}
+// rows [first batch `batch0` of U * RP rows onwards) -- batch0 = 1 after a caller fetched and committed batch 0 itself
+template <int T, int NW>
+__device__ __forceinline__ void load_tile(float* __restrict__ dst, const float* __restrict__ src /* row 0 of the sample */, int R, long V, long v0, int batch0 = 0) {
+    constexpr int RP = 4 * NW, U = T == 4 ? 4 : 8;       // 16-byte requests: four per thread in flight carry as many bytes as sixteen 4-byte ones
+    for (int row0 = (threadIdx.x >> 4) + batch0 * U * RP; row0 < R; row0 += U * RP) {
+        typename TileVec<T>::type t[U];
+        tile_fetch<T, NW, U>(t, src, R, V, v0, row0);
+        tile_commit<T, NW, U>(dst, t, R, V, v0, row0);
     }
 }
 
 // per-voxel statistics of the LDS tile X[C][S] over the channel axis (two passes); every thread returns those of ITS column col = tid % NT.
-// red: NP * NT floats of scratch.  Ends with a barrier-free state: callers must __syncthreads() before overwriting red again.
+// red: NP * NT floats of scratch.  Ends with a barrier-free state: callers must vx_bar() before overwriting red again.
 template <int T, int NW>
 __device__ __forceinline__ void tile_ln_stats(const float* __restrict__ X, int C, float eps, float* __restrict__ red, float& mean, float& rstd) {
     constexpr int NT = Geo<T>::NT, S = Geo<T>::S, NP = 64 * NW / NT;
@@ -145,16 +276,16 @@ __device__ __forceinline__ void tile_ln_stats(const float* __restrict__ X, int C
     float s = 0.0f;
     for (int c = part; c < C; c += NP) s += X[c * S + col];
     red[part * NT + col] = s;
-    __syncthreads();
+    vx_bar();
     float tot = 0.0f;
 #pragma unroll 4
     for (int p_ = 0; p_ < NP; ++p_) tot += red[p_ * NT + col];
     mean = tot / (float)C;
-    __syncthreads();
+    vx_bar();
     float qq = 0.0f;
     for (int c = part; c < C; c += NP) { const float d = X[c * S + col] - mean; qq = fmaf(d, d, qq); }
     red[part * NT + col] = qq;
-    __syncthreads();
+    vx_bar();
     float var = 0.0f;
 #pragma unroll 4
     for (int p_ = 0; p_ < NP; ++p_) var += red[p_ * NT + col];
@@ -239,8 +370,10 @@ __device__ __forceinline__ void stage_vec(float* __restrict__ dst, const float* 
     for (int i = threadIdx.x; i < n; i += 64 * NW) dst[i] = src ? src[i] : fill;
 }
 
+// (second launch bound = waves per SIMD to compile for: the T = 4 instance runs the 32^3 level, 16 blocks per CU whose time is memory latency, so residency is what
+// hides it; 6 (5 for the backward) is the most the allocator reaches without scratch)
 template <int T, int NW>
-__global__ void __launch_bounds__(64 * NW) vx_ln_pw_fwd_k(VxLnPw p) {
+__global__ void __launch_bounds__(64 * NW, (T == 4 ? 6 : 1)) vx_ln_pw_fwd_k(VxLnPw p) {
     constexpr int NT = Geo<T>::NT, S = Geo<T>::S, NP = 64 * NW / NT;
     extern __shared__ __attribute__((aligned(16))) float vx_pf_lds[];
     const VxLnPwMod& M = p.m[blockIdx.y];
@@ -253,6 +386,19 @@ __global__ void __launch_bounds__(64 * NW) vx_ln_pw_fwd_k(VxLnPw p) {
     float* __restrict__ bia = bet + C;               // Jt
     const int b = blockIdx.x / p.tiles_per_b;
     const long V = p.V, v0 = (long)(blockIdx.x % p.tiles_per_b) * NT;
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    // the projections are ONE product over the Jt concatenated output rows (J[s] % 16 == 0: a row tile lies in one projection), so that the waves share
+    // sum J / 16 row tiles instead of running the projections one after the other -- at C = 16 each of those had a single tile, on wave 0
+    const int J0 = p.J[0], J01 = J0 + p.J[1];
+    const float* const w0 = M.w[0], *const w1 = M.w[1], *const w2 = M.w[2];
+    auto wrow = [&](int mt, int) {
+        const int m0 = 16 * mt;
+        return m0 < J0 ? w0 + (long)(m0 + r) * C : (m0 < J01 ? w1 + (long)(m0 - J0 + r) * C : w2 + (long)(m0 - J01 + r) * C);
+    };
+    AFrag fa;
+    const bool k16 = T == 4 && C == 16;              // the 32^3 level: K = 16 is ONE 16-k piece, requested once (a 64-k chunk asked for it four times)
+    if constexpr (T == 4) { if (k16) tile_gemm_first<false, 1>(fa, threadIdx.x >> 6, C, 1, Jt, wrow); }
+    if (!k16) tile_gemm_first<false, 4>(fa, threadIdx.x >> 6, C, 1, Jt, wrow);
     stage_vec<NW>(gam, M.gamma, C, 1.0f);
     stage_vec<NW>(bet, M.beta, C, 0.0f);
     {
@@ -263,7 +409,7 @@ __global__ void __launch_bounds__(64 * NW) vx_ln_pw_fwd_k(VxLnPw p) {
         if (p.s2d) load_tile_s2d<T, NW>(X, M.x + (long)b * C * V, C, p.C0, p.gh, p.gw, V, v0);      // (C0 * 8 V fine elements per sample = C * V)
         else load_tile<T, NW>(X, M.x + (long)b * C * V, C, V, v0);
     } else load_tile<T, NW>(X, M.x + (long)b * C * V, C, V, v0);
-    __syncthreads();
+    vx_bar();
     float mean, rstd;
     tile_ln_stats<T, NW>(X, C, p.eps, red, mean, rstd);
     {
@@ -276,29 +422,26 @@ __global__ void __launch_bounds__(64 * NW) vx_ln_pw_fwd_k(VxLnPw p) {
             if (xn && live) xn[(long)c * V] = n;
         }
     }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
-    int j0 = 0;
-    for (int sg = 0; sg < p.NS; ++sg) {
-        const int J = p.J[sg];
-        const float* __restrict__ bias = bia + j0;
-        float* __restrict__ out = M.out[sg] + (long)b * J * V;
-        tile_gemm1<T, NW, false>(M.w[sg], C, C, 1, J, X, [&](int mt, vx_f32x4 (&acc)[T]) {
+    vx_bar();
+    auto epi = [&](int mt, vx_f32x4 (&acc)[T]) {
+        const int m0 = 16 * mt;
+        const int sg = m0 < J0 ? 0 : (m0 < J01 ? 1 : 2), joff = sg == 0 ? 0 : (sg == 1 ? J0 : J01), J = sg == 0 ? J0 + 0 : (sg == 1 ? J01 - J0 : Jt - J01);      // (values, not a choice between objects: that one went through scratch)
+        float* __restrict__ out = (sg == 0 ? M.out[0] : (sg == 1 ? M.out[1] : M.out[2])) + (long)b * J * V;
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int m = 16 * mt + 4 * q + reg;
-                const float bb = bias[m];
-                if constexpr (T == 4) {
-                    const long v = v0 + 4 * r;
-                    if (v < V) *reinterpret_cast<float4*>(out + (long)m * V + v) = make_float4(acc[0][reg] + bb, acc[1][reg] + bb, acc[2][reg] + bb, acc[3][reg] + bb);
-                } else {
-                    const long v = v0 + r;
-                    if (v < V) out[(long)m * V + v] = acc[0][reg] + bb;
-                }
+        for (int reg = 0; reg < 4; ++reg) {
+            const int m = m0 - joff + 4 * q + reg;      // row of this projection
+            const float bb = bia[joff + m];
+            if constexpr (T == 4) {
+                const long v = v0 + 4 * r;
+                if (v < V) *reinterpret_cast<float4*>(out + (long)m * V + v) = make_float4(acc[0][reg] + bb, acc[1][reg] + bb, acc[2][reg] + bb, acc[3][reg] + bb);
+            } else {
+                const long v = v0 + r;
+                if (v < V) out[(long)m * V + v] = acc[0][reg] + bb;
             }
-        });
-        j0 += J;
-    }
+        }
+    };
+    if constexpr (T == 4) { if (k16) tile_gemm<T, T, false, 1>(fa, threadIdx.x >> 6, NW, 0, 1, C, 0, 0, 1, Jt, wrow, X, epi); }
+    if (!k16) tile_gemm<T, T, false, 4>(fa, threadIdx.x >> 6, NW, 0, 1, C, 0, 0, 1, Jt, wrow, X, epi);
 }
 
 // backward: dxn = sum_s W_s^T dout_s ;  dx = dres + LN'(dxn) ;  per-block partial sums of dgamma / dbeta -> part[(mod-local block) * 2C + {c, C + c}]
@@ -321,7 +464,7 @@ struct VxLnPwBwd {
 };
 
 template <int T, int NW>
-__global__ void __launch_bounds__(64 * NW) vx_ln_pw_bwd_k(VxLnPwBwd p) {
+__global__ void __launch_bounds__(64 * NW, (T == 4 ? 5 : 1)) vx_ln_pw_bwd_k(VxLnPwBwd p) {      // (5: as for the forward)
     constexpr int NT = Geo<T>::NT, S = Geo<T>::S, NP = 64 * NW / NT;
     extern __shared__ __attribute__((aligned(16))) float vx_pf_lds[];
     const VxLnPwBwdMod& M = p.m[blockIdx.y];
@@ -335,6 +478,25 @@ __global__ void __launch_bounds__(64 * NW) vx_ln_pw_bwd_k(VxLnPwBwd p) {
     float* __restrict__ gam = red + 2 * NP * NT;     // C
     const int b = blockIdx.x / p.tiles_per_b;
     const long V = p.V, v0 = (long)(blockIdx.x % p.tiles_per_b) * NT;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    // sharing of the ONE product dxn = sum_s W_s^T dout_s (C / 16 row tiles): with fewer row tiles than waves the four n-tiles of a T = 4 tile go to different waves
+    const int tiles = C >> 4;
+    const int nsp = (T == 4 && 4 * tiles <= NW) ? 4 : ((T == 4 && 2 * tiles <= NW) ? 2 : 1);
+    const int WG = NW / nsp, wl = wave % WG;
+    const float* const w0 = M.w[0], *const w1 = M.w[1], *const w2 = M.w[2];
+    auto wrow = [&](int mt, int sg) { return (sg == 0 ? w0 : (sg == 1 ? w1 : w2)) + 16 * mt + r; };
+    AFrag fa;
+    if constexpr (T == 4) {                                    // (T = 1 keeps the sequential product below: the look-ahead measured slower on the 8^3 / 4^3 grids)
+        if (nsp == 4) tile_gemm_first<true, 1>(fa, wl, p.J[0], C, C, wrow);      // (one row tile: 16-k pieces, see the forward)
+        else tile_gemm_first<true, 4>(fa, wl, p.J[0], C, C, wrow);
+    }
+    // T = 4: the residual gradient is requested with the first loads and waits in registers (RU rows per thread: C <= 64); wider tiles and T = 1 load it after the
+    // product as before
+    constexpr int RU = 4, RP = 4 * NW;
+    const bool has_res = M.dres != nullptr && Jt >= C;         // Jt >= C always holds for the PWA projections (2 ch_qk + ch_v >= C)
+    const bool res_early = T == 4 && has_res && C <= RU * RP;
+    typename TileVec<T>::type tres[RU];
+    if (res_early) tile_fetch<T, NW, RU>(tres, M.dres + (long)b * C * V, C, V, v0, threadIdx.x >> 4);
     stage_vec<NW>(gam, M.gamma, C, 1.0f);
     {
         int j0 = 0;
@@ -347,24 +509,37 @@ __global__ void __launch_bounds__(64 * NW) vx_ln_pw_bwd_k(VxLnPwBwd p) {
         if (p.s2d) load_tile_s2d<T, NW>(X, M.x + (long)b * C * V, C, p.C0, p.gh, p.gw, V, v0);
         else load_tile<T, NW>(X, M.x + (long)b * C * V, C, V, v0);
     } else load_tile<T, NW>(X, M.x + (long)b * C * V, C, V, v0);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
-    {
+    vx_bar();
+    if constexpr (T == 4) {
+        if (nsp == 4) {
+            tile_gemm<T, 1, true, 1>(fa, wl, WG, wave / WG, p.NS, p.J[0], p.J[1], p.J[2], C, C, wrow, D, [&](int mt, vx_f32x4 (&acc)[1]) {
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) G[(16 * mt + 4 * q + reg) * S + 4 * r + wave / WG] = acc[0][reg];
+            });
+        } else if (nsp == 2) {
+            tile_gemm<T, 2, true, 4>(fa, wl, WG, 2 * (wave / WG), p.NS, p.J[0], p.J[1], p.J[2], C, C, wrow, D, [&](int mt, vx_f32x4 (&acc)[2]) {
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) *reinterpret_cast<float2*>(G + (16 * mt + 4 * q + reg) * S + 4 * r + 2 * (wave / WG)) = make_float2(acc[0][reg], acc[1][reg]);
+            });
+        }
+        if (nsp == 1) {
+            tile_gemm<T, T, true, 4>(fa, wl, WG, 0, p.NS, p.J[0], p.J[1], p.J[2], C, C, wrow, D, [&](int mt, vx_f32x4 (&acc)[T]) {
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) *reinterpret_cast<float4*>(G + (16 * mt + 4 * q + reg) * S + 4 * r) = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);
+            });
+        }
+    } else {
         const float* const ws[3] = {M.w[0], M.w[1], M.w[2]};
         const int ks[3] = {p.J[0], p.J[1], p.J[2]};
-        tile_gemm<T, NW, true>(p.NS, ws, ks, 1, C, C, D, [&](int mt, vx_f32x4 (&acc)[T]) {
+        tile_gemm_seq<T, NW, true>(p.NS, ws, ks, 1, C, C, D, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int m = 16 * mt + 4 * q + reg;
-                if constexpr (T == 4) *reinterpret_cast<float4*>(G + m * S + 4 * r) = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);
-                else G[m * S + r] = acc[0][reg];
-            }
+            for (int reg = 0; reg < 4; ++reg) G[(16 * mt + 4 * q + reg) * S + r] = acc[0][reg];
         });
     }
     float mean, rstd;
     tile_ln_stats<T, NW>(X, C, p.eps, red, mean, rstd);        // (its first barrier also publishes G and retires every read of D)
-    const bool has_res = M.dres != nullptr && Jt >= C;         // Jt >= C always holds for the PWA projections (2 ch_qk + ch_v >= C)
-    if (has_res) load_tile<T, NW>(D, M.dres + (long)b * C * V, C, V, v0);
+    if (res_early) tile_commit<T, NW, RU>(D, tres, C, V, v0, threadIdx.x >> 4);
+    else if (has_res) load_tile<T, NW>(D, M.dres + (long)b * C * V, C, V, v0);
     const int col = threadIdx.x % NT, part = threadIdx.x / NT;
     float s1 = 0.0f, s2 = 0.0f;
     for (int c = part; c < C; c += NP) {
@@ -373,10 +548,10 @@ __global__ void __launch_bounds__(64 * NW) vx_ln_pw_bwd_k(VxLnPwBwd p) {
         s1 += g;
         s2 = fmaf(g, xh, s2);
     }
-    __syncthreads();                                           // red is re-used; the dres tile is published
+    vx_bar();                                           // red is re-used; the dres tile is published
     red[part * NT + col] = s1;
     red[(NP + part) * NT + col] = s2;
-    __syncthreads();
+    vx_bar();
     float t1 = 0.0f, t2 = 0.0f;
 #pragma unroll 4
     for (int p_ = 0; p_ < NP; ++p_) { t1 += red[p_ * NT + col]; t2 += red[(NP + p_) * NT + col]; }
@@ -473,15 +648,17 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_fwd_k(VxPost p) {
     stage_vec<NW>(bet, M.beta, C, 0.0f);
     stage_vec<NW>(b2, M.b2, C, 0.0f);
     stage_vec<NW>(b1, M.b1, R, 0.0f);
+    AFrag fa;
+    tile_gemm1_first<NW, false>(fa, M.wm, Cv, Cv, 1, C);
     load_tile<T, NW>(Sx, M.s + (long)b * Cv * V, Cv, V, v0);
     load_tile<T, NW>(Y, M.x + (long)b * C * V, C, V, v0);
-    __syncthreads();
+    vx_bar();
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const int cr = T * r;                            // first tile column of this lane's accumulator elements
     const long v = v0 + cr;
     const bool vlive = v < V;                        // (T = 4: V % 4 == 0, the four voxels live or die together)
     // y = alpha x + drop(Wm s + bm)          (element (m, r) of Y is read and written by its owner only)
-    tile_gemm1<T, NW, false>(M.wm, Cv, Cv, 1, C, Sx, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1<T, NW, false>(fa, M.wm, Cv, Cv, 1, C, Sx, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int m = 16 * mt + 4 * q + reg;
@@ -500,16 +677,17 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_fwd_k(VxPost p) {
             stv<T>(Y + m * S + cr, yv);
         }
     });
-    __syncthreads();
+    tile_gemm1_first<NW, false>(fa, M.w1, C, C, 1, R);      // (the next product's first weights, ahead of the barrier)
+    vx_bar();
     float mean, rstd;
     tile_ln_stats<T, NW>(Y, C, p.eps, red, mean, rstd);
     {
         const int col = threadIdx.x % NT, part = threadIdx.x / NT;
         for (int c = part; c < C; c += NP) N[c * S + col] = fmaf(gam[c], (Y[c * S + col] - mean) * rstd, bet[c]);
     }
-    __syncthreads();
+    vx_bar();
     // h = drop1(gelu(W1 n + b1))
-    tile_gemm1<T, NW, false>(M.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1<T, NW, false>(fa, M.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int j = 16 * mt + 4 * q + reg;
@@ -525,9 +703,10 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_fwd_k(VxPost p) {
             stv<T>(Hh + j * S + cr, hv);
         }
     });
-    __syncthreads();
+    tile_gemm1_first<NW, false>(fa, M.w2, R, R, 1, C);      // (the next product's first weights, ahead of the barrier)
+    vx_bar();
     // out = y + drop2(W2 h + b2)
-    tile_gemm1<T, NW, false>(M.w2, R, R, 1, C, Hh, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1<T, NW, false>(fa, M.w2, R, R, 1, C, Hh, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int m = 16 * mt + 4 * q + reg;
@@ -605,7 +784,7 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_bwd_k(VxPost p) {
     const long v = v0 + cr;
     const bool vlive = v < V;
     // a = W1 n + b1 ; h = drop1(gelu(a)) -> global (dW2's operand)
-    tile_gemm1<T, NW, false>(M.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, false>(M.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int j = 16 * mt + 4 * q + reg;
@@ -625,7 +804,7 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_bwd_k(VxPost p) {
     });
     __syncthreads();
     // da = (W2^T dz) * mask1 * gelu'(a)      (each accumulator element meets its own a: same (row, column) ownership as the stage above)
-    tile_gemm1<T, NW, true>(M.w2, C, 1, R, R, DZ, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, true>(M.w2, C, 1, R, R, DZ, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int j = 16 * mt + 4 * q + reg;
@@ -647,7 +826,7 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_bwd_k(VxPost p) {
     });
     __syncthreads();
     // dn = W1^T da  -> DZ (dz is no longer needed)
-    tile_gemm1<T, NW, true>(M.w1, R, 1, C, C, A, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, true>(M.w1, R, 1, C, C, A, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             float dn[T];
@@ -709,7 +888,7 @@ __global__ void __launch_bounds__(64 * NW) vx_pwa_post_bwd_k(VxPost p) {
     }
     __syncthreads();
     // ds = Wm^T dmix
-    tile_gemm1<T, NW, true>(M.wm, C, 1, Cv, Cv, N, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, true>(M.wm, C, 1, Cv, Cv, N, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int m = 16 * mt + 4 * q + reg;
@@ -928,7 +1107,14 @@ __device__ __forceinline__ void inmlp_stats(const VxInMlp& p, int b, float* __re
         if (p.part != nullptr) {
             double s = 0.0, q = 0.0;
             const double* pp = p.part + bc * p.nparts * 2;
-            for (int i = 0; i < p.nparts; ++i) { s += pp[2 * i]; q += pp[2 * i + 1]; }
+            // eight partials in flight per trip (the loads do not depend on the sums); the fold itself is the same fp64 expression in the same order
+            for (int i0 = 0; i0 < p.nparts; i0 += 8) {
+                double ls[8], lq[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int i = min(i0 + u, p.nparts - 1); ls[u] = pp[2 * i]; lq[u] = pp[2 * i + 1]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) if (i0 + u < p.nparts) { s += ls[u]; q += lq[u]; }
+            }
             const double m = s / (double)p.V;
             double var = q / (double)p.V - m * m;
             var = var < 0.0 ? 0.0 : var;
@@ -957,28 +1143,35 @@ __global__ void __launch_bounds__(64 * NW) vx_inmlp_fwd_k(VxInMlp p) {
     const int b = blockIdx.x / p.tiles_per_b, tile = blockIdx.x % p.tiles_per_b;
     const long V = p.V, v0 = (long)tile * NT;
     const VxDropCtx d2 = drop_ctx_dev(p.seed_ptr, p.site, p.p);
+    // the tile (its first 32 NW rows) and the first weights are requested before the statistics fold, which waits for its own global loads
+    AFrag fa;
+    tile_gemm1_first<NW, false>(fa, p.w1, C, C, 1, R);
+    float t0[8];
+    tile_fetch<T, NW, 8>(t0, p.o + (long)b * C * V, C, V, v0, threadIdx.x >> 4);
     inmlp_stats<NW>(p, b, mu, rs, tile == 0);
     stage_vec<NW>(b2, p.b2, C, 0.0f);
     stage_vec<NW>(b1, p.b1, R, 0.0f);
-    load_tile<T, NW>(O, p.o + (long)b * C * V, C, V, v0);
-    __syncthreads();
+    tile_commit<T, NW, 8>(O, t0, C, V, v0, threadIdx.x >> 4);
+    load_tile<T, NW>(O, p.o + (long)b * C * V, C, V, v0, 1);
+    vx_bar();
     {
         const int col = threadIdx.x % NT, part = threadIdx.x / NT;
         for (int c = part; c < C; c += NP) N[c * S + col] = (O[c * S + col] - mu[c]) * rs[c];
     }
-    __syncthreads();
+    vx_bar();
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const long v = v0 + r;
     const bool vlive = v < V;
-    tile_gemm1<T, NW, false>(p.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1<T, NW, false>(fa, p.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int j = 16 * mt + 4 * q + reg;
             Hh[j * S + r] = vlive ? vx_gelu_fast(acc[0][reg] + b1[j]) : 0.0f;
         }
     });
-    __syncthreads();
-    tile_gemm1<T, NW, false>(p.w2, R, R, 1, C, Hh, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_first<NW, false>(fa, p.w2, R, R, 1, C);      // (the next product's first weights, ahead of the barrier)
+    vx_bar();
+    tile_gemm1<T, NW, false>(fa, p.w2, R, R, 1, C, Hh, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int m = 16 * mt + 4 * q + reg;
@@ -1022,7 +1215,7 @@ __global__ void __launch_bounds__(64 * NW) vx_inmlp_bwd_k(VxInMlp p) {
     const long v = v0 + r;
     const bool vlive = v < V;
     // a = W1 nhat + b1 ; h = gelu(a) -> global (dW2's operand)
-    tile_gemm1<T, NW, false>(p.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, false>(p.w1, C, C, 1, R, N, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int j = 16 * mt + 4 * q + reg;
@@ -1033,7 +1226,7 @@ __global__ void __launch_bounds__(64 * NW) vx_inmlp_bwd_k(VxInMlp p) {
     });
     __syncthreads();
     // da = (W2^T dz) * gelu'(a)
-    tile_gemm1<T, NW, true>(p.w2, C, 1, R, R, DZ, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, true>(p.w2, C, 1, R, R, DZ, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int j = 16 * mt + 4 * q + reg;
@@ -1044,7 +1237,7 @@ __global__ void __launch_bounds__(64 * NW) vx_inmlp_bwd_k(VxInMlp p) {
     });
     __syncthreads();
     // dn = W1^T da -> global, and this tile's (sum dn, sum dn nhat) per channel: the 16 voxels of an accumulator register are the 16 lanes of a q group
-    tile_gemm1<T, NW, true>(p.w1, R, 1, C, C, A, [&](int mt, vx_f32x4 (&acc)[T]) {
+    tile_gemm1_seq<T, NW, true>(p.w1, R, 1, C, C, A, [&](int mt, vx_f32x4 (&acc)[T]) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int m = 16 * mt + 4 * q + reg;
