@@ -659,6 +659,12 @@ int vx_key_histogram(const float* x, const void* mask, int mask_bytes, long n, l
  * all fp32.  mode 1: gather through i0 (i1 and w may be NULL).  out must not alias x.  The label variant copies elements of 1 / 4 / 8 bytes (code -4 = 4) bit for bit. */
 int vx_resample_axes(const float* x, float* out, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, const int* i1, const float* w, int mode, void* stream);
 int vx_resample_axes_label(const void* x, void* out, int lab_bytes, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, void* stream);
+/* Label map on another grid, straight from the logits: labels[zo, yo, xo] = arg-max over the C classes of the trilinear value that
+ * vx_resample_axes (mode 0) forms from logits (C, D, H, W) with the same tables -- the same clamped indices, the same seven fmaf in the same order -- under the
+ * arg-max rule of vx_sw_finalize (first NaN, else first maximum, -0.0 == +0.0).  labels (Do, Ho, Wo) uint8 therefore equals vx_argmax_channels of the resampled
+ * volume byte for byte, NaN and inf included, and no fp32 volume on the output grid is written.  1 <= C <= 256; labels needs no alignment (one byte per lane
+ * is stored).  Checked before the launch (-1): pointers, extents, C. */
+int vx_native_argmax(const float* logits, unsigned char* labels, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, const int* i1, const float* w, void* stream);
 
 /* ---- connected components (csrc/components.hip): labelling, per-component tallies, keep / drop filter ------------------------------
  * No counterpart in the reference (its metrics are per voxel).  One sample per call; label maps are uint8 / int32 / int64 (bytes 1 / 4 / 8, compared as raw

@@ -233,6 +233,66 @@ __global__ void __launch_bounds__(256) vx_resample_axes_label_k(const T* __restr
     for (int xo = (int)(threadIdx.x & 63); xo < Wo; xo += 64) orow[xo] = r[vx_clampi(x0t[xo], W)];
 }
 
+// One output row of vx_native_argmax_k.  ZS / YS: the row's two z / y source indices are the same (a clamped edge, a volume one voxel thick): the second plane / row
+// would load the bytes the first one has loaded, so its lerps are taken over instead of formed again -- the same values, the same seven fmaf, half or a quarter of the gathers.
+template <bool ZS, bool YS>
+__device__ __forceinline__ void vx_native_argmax_row(const float* __restrict__ x, unsigned char* __restrict__ orow, int C, long Vi, int W, int Wo, int lane, long o00, long o01,
+                                                     long o10, long o11, float wy, float wz, const int* __restrict__ x0t, const int* __restrict__ x1t, const float* __restrict__ wxt) {
+    for (int xo = lane; xo < Wo; xo += 64) {
+        const int x0 = vx_clampi(x0t[xo], W), x1 = vx_clampi(x1t[xo], W);
+        const float wx = wxt[xo];
+        float best = -INFINITY;
+        int arg = 0;
+        const float* __restrict__ xc = x;
+        for (int c = 0; c < C; ++c, xc += Vi) {
+            const float a00 = xc[o00 + x0];
+            const float l00 = fmaf(wx, xc[o00 + x1] - a00, a00);
+            float l01 = l00, l10 = l00, l11 = l00;
+            if (!YS) { const float a01 = xc[o01 + x0]; l01 = fmaf(wx, xc[o01 + x1] - a01, a01); }
+            if (!ZS) {
+                const float a10 = xc[o10 + x0];
+                l10 = fmaf(wx, xc[o10 + x1] - a10, a10);
+                l11 = l10;
+                if (!YS) { const float a11 = xc[o11 + x0]; l11 = fmaf(wx, xc[o11 + x1] - a11, a11); }
+            } else {
+                l11 = l01;
+            }
+            const float m0 = fmaf(wy, l01 - l00, l00);
+            const float m1 = ZS ? m0 : fmaf(wy, l11 - l10, l10);
+            const float q = fmaf(wz, m1 - m0, m0);
+            if (q > best || (q != q && !(best != best))) { best = q; arg = c; }          // NaN ranks highest, first occurrence wins
+        }
+        orow[xo] = (unsigned char)arg;
+    }
+}
+
+// labels[zo, yo, xo] = arg-max over c of the trilinear value vx_resample_axes_k forms for (c, zo, yo, xo): the same clamped indices and the same seven fmaf in the same
+// order, so the label is that of vx_argmax_channels on the resampled volume, which is never written.  One wave per output row (zo, yo) as above, the lanes walk x (their
+// gathers of a source row are contiguous); the classes are walked in registers with a running best (first NaN, else first maximum: the rule of vx_sw_finalize_k); one
+// byte per lane is stored.  (A form with four consecutive voxels per lane and one 32-bit store was measured 2.3 - 2.4 times slower: DESIGN.md section 27.)
+__global__ void __launch_bounds__(256) vx_native_argmax_k(const float* __restrict__ x, unsigned char* __restrict__ labels, int C, long Vi, long rows, int D, int H, int W,
+                                                          int Do, int Ho, int Wo, const int* __restrict__ i0, const int* __restrict__ i1, const float* __restrict__ w) {
+    const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (row >= rows) return;
+    const int yo = (int)(row % Ho), zo = (int)(row / Ho);
+    const int lane = threadIdx.x & 63;
+    const int z0 = vx_clampi(i0[zo], D), y0 = vx_clampi(i0[Do + yo], H);
+    const int z1 = vx_clampi(i1[zo], D), y1 = vx_clampi(i1[Do + yo], H);
+    const float wz = w[zo], wy = w[Do + yo];
+    const int* __restrict__ x0t = i0 + Do + Ho;
+    const int* __restrict__ x1t = i1 + Do + Ho;
+    const float* __restrict__ wxt = w + Do + Ho;
+    const long o00 = ((long)z0 * H + y0) * W, o01 = ((long)z0 * H + y1) * W, o10 = ((long)z1 * H + y0) * W, o11 = ((long)z1 * H + y1) * W;
+    unsigned char* __restrict__ orow = labels + row * Wo;
+    if (z1 == z0) {          // wave-uniform: z0, z1, y0, y1 come from scalar loads
+        if (y1 == y0) vx_native_argmax_row<true, true>(x, orow, C, Vi, W, Wo, lane, o00, o01, o10, o11, wy, wz, x0t, x1t, wxt);
+        else vx_native_argmax_row<true, false>(x, orow, C, Vi, W, Wo, lane, o00, o01, o10, o11, wy, wz, x0t, x1t, wxt);
+    } else {
+        if (y1 == y0) vx_native_argmax_row<false, true>(x, orow, C, Vi, W, Wo, lane, o00, o01, o10, o11, wy, wz, x0t, x1t, wxt);
+        else vx_native_argmax_row<false, false>(x, orow, C, Vi, W, Wo, lane, o00, o01, o10, o11, wy, wz, x0t, x1t, wxt);
+    }
+}
+
 static inline int vx_stream_grid(long n, int cap) { const long g = (n + 255) / 256; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
 
 extern "C" int vx_moments_blocks(void) { return VX_MOM_BLOCKS; }
@@ -339,5 +399,19 @@ extern "C" int vx_resample_axes_label(const void* x, void* out, int lab_bytes, i
     else if (lab_bytes == 8) vx_resample_axes_label_k<unsigned long long><<<g, b, 0, st>>>((const unsigned long long*)x, (unsigned long long*)out, Vi, total, D, H, W, Do, Ho, Wo, i0);
     else VX_FAIL(-3, "vx_resample_axes_label: label width %d bytes not supported", lab_bytes);
     VX_LAUNCH_CHECK("vx_resample_axes_label");
+    return 0;
+}
+
+extern "C" int vx_native_argmax(const float* logits, unsigned char* labels, int C, int D, int H, int W, int Do, int Ho, int Wo, const int* i0, const int* i1, const float* w,
+                                void* stream) {
+    VX_REQUIRE(logits && labels && i0 && i1 && w, "vx_native_argmax: bad args (null pointer)");
+    VX_REQUIRE(C >= 1 && C <= 256, "vx_native_argmax: %d classes (1 .. 256 fit a uint8 label)", C);
+    VX_REQUIRE(D > 0 && H > 0 && W > 0 && Do > 0 && Ho > 0 && Wo > 0, "vx_native_argmax: bad sizes");
+    const long rows = (long)Do * Ho;          // output rows: one wave each
+    VX_REQUIRE((rows + 3) / 4 <= 0x7fffffffL, "vx_native_argmax: output of %ld rows is too large for one launch", rows);
+    const dim3 g((unsigned)((rows + 3) / 4)), b(256);
+    const long Vi = (long)D * H * W;
+    vx_native_argmax_k<<<g, b, 0, (hipStream_t)stream>>>(logits, labels, C, Vi, rows, D, H, W, Do, Ho, Wo, i0, i1, w);
+    VX_LAUNCH_CHECK("vx_native_argmax");
     return 0;
 }

@@ -463,7 +463,7 @@ class Net(torch.nn.Module):
 
 @torch.inference_mode()
 def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequence[int], sw_batch_size: int, overlap: float, taped: bool = True, postprocess=None,
-                 mirror_axes: Sequence[int] = (), blend: str = "constant", sigma_scale=0.125):
+                 mirror_axes: Sequence[int] = (), blend: str = "constant", sigma_scale=0.125, native=None):
     """eval-mode sliding-window segmentation of one (B, C, D, H, W) volume -> (blended logits, uint8 label map).
     postprocess (a utils.components.Postprocess, or the dict its from_config takes): the returned label map is the cleaned-up one (components below a voxel
     count dropped / the k largest kept, on the GPU); the returned logits are untouched.
@@ -473,7 +473,14 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
     when the parameters / buffers were re-homed since the capture (TrainEngine's flat buffer, .to(), a parameter swap): a tape bakes in raw
     device pointers.
     mirror_axes: mirror test-time augmentation (sliding_window_inference); mirrored windows have the window's shape and replay the same tape and replicas.
-    blend, sigma_scale: constant or Gaussian importance blending (sliding_window_inference); the forwards, their tapes and replicas are the same for both."""
+    blend, sigma_scale: constant or Gaussian importance blending (sliding_window_inference); the forwards, their tapes and replicas are the same for both.
+    native: None (every launch is the one of the call without the keyword), or {"native_shape": (D, H, W), "native_spacing", "net_spacing"} for a volume that was
+    resampled to the network's spacing (utils.preprocess.Spacingd): the returned label map is then on the image's OWN grid, (B, 1, *native_shape), formed from the
+    blended logits by utils.preprocess.labels_on_native_grid (one kernel per batch item, no float volume on the native grid).  postprocess runs on those labels:
+    its voxel-count thresholds are in NATIVE voxels.  The returned logits stay on the network grid, untouched.  A bad dict raises before any GPU work."""
+    if native is not None:
+        from .preprocess import check_native_geometry
+        native = check_native_geometry(native)
     was_training = model.training
     model.eval()
     try:
@@ -486,8 +493,13 @@ def infer_volume(model: torch.nn.Module, volume: torch.Tensor, roi_size: Sequenc
             if pred is None:
                 pred = TapedPredictor(net)
                 model.__dict__["_vx_taped_predictor"] = pred       # plain attribute (not a sub-module): dies with the model
-        logits, labels = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=True, mirror_axes=mirror_axes, blend=blend,
-                                                  sigma_scale=sigma_scale)
+        out = sliding_window_inference(volume, roi_size, sw_batch_size, pred, overlap=overlap, return_labels=native is None, mirror_axes=mirror_axes, blend=blend,
+                                       sigma_scale=sigma_scale)
+        logits, labels = out if native is None else (out, None)
+        if native is not None:
+            from .preprocess import labels_on_native_grid
+            labels = torch.stack([labels_on_native_grid(logits[b], native["native_shape"], native["net_spacing"], native["native_spacing"])
+                                  for b in range(logits.shape[0])])[:, None]
         if postprocess is not None:
             from .components import Postprocess
             labels = (postprocess if isinstance(postprocess, Postprocess) else Postprocess.from_config(postprocess))(labels)

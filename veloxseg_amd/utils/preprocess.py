@@ -13,6 +13,9 @@ Two things a user has to know:
 * `resample_to_spacing` / `Spacingd` restate MONAI's `Spacing` for axis-aligned affines (output size round((n - 1) src / dst + 1), output index j samples
   input coordinate j src / dst, border clamp).  MONAI is not available here, so this is UNPINNED against MONAI itself, like oracle/augment_oracle.py.
 
+* The way back: `inverse_tables` / `resample_to_shape` / `labels_on_native_grid` take a prediction from the network grid to the image's own grid with the SAME coordinate
+  rule, the native extent given instead of computed; the label map comes from one kernel that interpolates the logits and keeps only their arg-max.
+
 `IntensityStatistics` takes THREE rounds over the dataset (11 + 11 + 10 key bits; the mean rides on round 1, the std on round 2, min / max on round 1)."""
 import math
 
@@ -321,22 +324,61 @@ def axis_table(n, n_out, src, dst, mode="bilinear"):
     return i0, np.minimum(i0 + 1, n - 1).astype(np.int32), (c - i0).astype(np.float32)
 
 
+def _shape3(v, what):
+    v = list(v.tolist() if hasattr(v, "tolist") else v)
+    if len(v) != 3 or any(isinstance(n, bool) or int(n) != n or int(n) < 1 for n in v):
+        raise ValueError(f"{what}: three positive integer extents expected, got {v}")
+    return tuple(int(n) for n in v)
+
+
+def inverse_tables(net_shape, native_shape, net_spacing, native_spacing, mode="bilinear"):
+    """the tables that take a volume on the network grid back to the image's own grid: per axis axis_table(n_net, n_native, src=net_spacing, dst=native_spacing,
+    mode).  The output extent is GIVEN (the native shape), not recomputed: where round() in output_shape did not invert, the native coordinates past the last network
+    voxel are clamped to n_net - 1 by axis_table (i0 = i1 = n_net - 1, w = 0)."""
+    net, nat = _shape3(net_shape, "net_shape"), _shape3(native_shape, "native_shape")
+    src, dst = _spacing3(net_spacing, "net_spacing"), _spacing3(native_spacing, "native_spacing")
+    return [axis_table(n, no, s, d, mode) for n, no, s, d in zip(net, nat, src, dst)]
+
+
+def check_native_geometry(native):
+    """the geometry of a volume that was resampled to the network's spacing, as infer_volume(native=) takes it: a dict with exactly the keys native_shape (three
+    positive integers), native_spacing and net_spacing (three positive finite numbers each) -> the same dict with tuples of int / float; anything else: ValueError"""
+    if not isinstance(native, dict) or set(native) != {"native_shape", "native_spacing", "net_spacing"}:
+        raise ValueError("native: a dict with exactly the keys native_shape, native_spacing, net_spacing expected")
+    return {"native_shape": _shape3(native["native_shape"], "native_shape"), "native_spacing": tuple(_spacing3(native["native_spacing"], "native_spacing")),
+            "net_spacing": tuple(_spacing3(native["net_spacing"], "net_spacing"))}
+
+
+def _device_tables(tabs, device, k):
+    return torch.from_numpy(np.concatenate([t[k] for t in tabs])).to(device)
+
+
 def resample_to_spacing(x: torch.Tensor, src_spacing, dst_spacing, mode: str = "bilinear") -> torch.Tensor:
     """(D, H, W) or (C, D, H, W) resampled from src_spacing to dst_spacing (one value per spatial axis, in the tensor's axis order).  "bilinear": float32, three
     nested lerps; "nearest": float32 or a label dtype (uint8, int32, int64), copied bit for bit."""
-    _need_cuda(x, "resample_to_spacing")
+    return _resample(x, None, src_spacing, dst_spacing, mode, "resample_to_spacing")
+
+
+def resample_to_shape(x: torch.Tensor, out_shape, src_spacing, dst_spacing, mode: str = "bilinear") -> torch.Tensor:
+    """resample_to_spacing with the output extent GIVEN (three integers) instead of computed from the spacings: the way back from the network grid to an image's own
+    grid (inverse_tables), for logits or any float map, and for labels with "nearest".  Output coordinates past the last input voxel are clamped to it."""
+    return _resample(x, out_shape, src_spacing, dst_spacing, mode, "resample_to_shape")
+
+
+def _resample(x, out_shape, src_spacing, dst_spacing, mode, what):
+    _need_cuda(x, what)
     if mode not in ("bilinear", "nearest"):
         raise ValueError(f"mode {mode!r} not supported (bilinear, nearest)")
     if x.dim() not in (3, 4) or x.numel() == 0:
-        raise ValueError(f"resample_to_spacing: expected a non-empty (D, H, W) or (C, D, H, W), got {tuple(x.shape)}")
+        raise ValueError(f"{what}: expected a non-empty (D, H, W) or (C, D, H, W), got {tuple(x.shape)}")
     src, dst = _spacing3(src_spacing, "src_spacing"), _spacing3(dst_spacing, "dst_spacing")
     if mode == "bilinear" and x.dtype != torch.float32:
-        raise TypeError(f"resample_to_spacing: bilinear needs float32, got {x.dtype}")
+        raise TypeError(f"{what}: bilinear needs float32, got {x.dtype}")
     code = label_code(x)
     xin = x.contiguous()
     C = 1 if x.dim() == 3 else x.shape[0]
     sp = tuple(x.shape[-3:])
-    so = output_shape(sp, src, dst)
+    so = output_shape(sp, src, dst) if out_shape is None else _shape3(out_shape, "out_shape")
     tabs = [axis_table(n, no, s, d, mode) for n, no, s, d in zip(sp, so, src, dst)]
     i0 = torch.from_numpy(np.concatenate([t[0] for t in tabs])).to(x.device)
     out = torch.empty(tuple(x.shape[:-3]) + so, dtype=x.dtype, device=x.device)
@@ -347,6 +389,31 @@ def resample_to_spacing(x: torch.Tensor, src_spacing, dst_spacing, mode: str = "
         H.call("vx_resample_axes", xin.data_ptr(), out.data_ptr(), C, *sp, *so, i0.data_ptr(), i1.data_ptr(), w.data_ptr(), 0 if mode == "bilinear" else 1, st)
     else:
         H.call("vx_resample_axes_label", xin.data_ptr(), out.data_ptr(), code, C, *sp, *so, i0.data_ptr(), st)
+    return out
+
+
+def labels_on_native_grid(logits: torch.Tensor, native_shape, net_spacing, native_spacing) -> torch.Tensor:
+    """the inverse of Spacingd for a prediction: (K, d, h, w) or (1, K, d, h, w) float32 logits on the network grid (spacing net_spacing) -> uint8 label map
+    (D, H, W) = native_shape on the image's own grid (spacing native_spacing), in ONE kernel (vx_native_argmax): per native voxel the K trilinear values are formed
+    in registers and only their arg-max is stored.  Byte for byte vx_argmax_channels(resample_to_shape(logits, native_shape, net_spacing, native_spacing)) -- first
+    NaN, else first maximum -- without the (K, D, H, W) float volume.  The LOGITS are interpolated, not soft-max probabilities (MONAI's Invertd followed by
+    AsDiscrete(argmax=True)).  K <= 256."""
+    _need_cuda(logits, "labels_on_native_grid")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"labels_on_native_grid: expected float32 logits, got {logits.dtype}")
+    if logits.dim() == 5 and logits.shape[0] == 1:
+        logits = logits[0]
+    if logits.dim() != 4 or logits.numel() == 0:
+        raise ValueError(f"labels_on_native_grid: expected non-empty (K, d, h, w) or (1, K, d, h, w) logits, got {tuple(logits.shape)}")
+    K, sp = int(logits.shape[0]), tuple(logits.shape[1:])
+    if K > 256:
+        raise ValueError(f"labels_on_native_grid: {K} classes do not fit a uint8 label map (at most 256)")
+    so = check_native_geometry({"native_shape": native_shape, "net_spacing": net_spacing, "native_spacing": native_spacing})["native_shape"]
+    tabs = inverse_tables(sp, so, net_spacing, native_spacing)
+    xin = logits.contiguous()
+    i0, i1, w = (_device_tables(tabs, xin.device, k) for k in range(3))
+    out = torch.empty(so, dtype=torch.uint8, device=xin.device)
+    H.call("vx_native_argmax", xin.data_ptr(), out.data_ptr(), K, *sp, *so, i0.data_ptr(), i1.data_ptr(), w.data_ptr(), H.stream_ptr())
     return out
 
 
