@@ -626,6 +626,31 @@ int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float co
 #define VX_AUG_NOISE_STREAM 0x564158475541ull      /* "AUGXAV": far above every dropout site id (those count up from 1, functional.new_dropout_site) */
 int vx_augment_batch(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream);
 
+/* ---- spatial augmentation (csrc/augment_affine.hip): 3-D affine resampling of any number of volumes in ONE launch ----
+ * `records` is a DEVICE table of n_records records of VX_AFFINE_RECORD_BYTES bytes; one record = one output volume (one channel of one key of one sample):
+ *   byte   0  uint64    source device pointer: element (0, 0, 0) of the WINDOW (a view into a larger volume is fine; any alignment of its element type)
+ *   byte   8  uint64    destination device pointer: a contiguous (Do, Ho, Wo) volume of the source's element type, not overlapping any source
+ *   byte  16  int64[3]  strides of the source over (D, H, W), in elements; each fits a signed 32-bit integer (a record with a wider stride writes nothing)
+ *   byte  40  int32[3]  n: extents of the window (the centre of the map is formed from them on the host; the kernel reads lo / hi)
+ *   byte  52  int32[3]  lo, byte 64 int32[3] hi: the valid index range in window coordinates, lo <= hi; 0 .. n-1, or -start .. parent-1-start for a crop view whose
+ *                       parent may be read outside the window ("context")
+ *   byte  76  int32     element type: 0 = fp32 image, or a label code 1 = uint8, 4 = int32, 8 = int64, -4 = float32
+ *   byte  80  int32     mode: 0 trilinear (fp32 only), 1 nearest
+ *   byte  84  int32     pad: 0 border (the coordinate is clamped to [lo, hi], then sampled), 1 constant (a corner / rounded index outside [lo, hi] gives cval)
+ *   byte  88  float     cval (converted to the element type with a C cast)
+ *   byte  92  float[9]  A, row-major, byte 128 float[3] c, byte 140 int32 unused
+ * Rule, per output voxel o = (o_0, o_1, o_2) of (Do, Ho, Wo), every operation rounded to fp32 on its own (nothing is contracted):
+ *   p_a = (float)o_a - 0.5f * (float)(Out_a - 1);   s_a = ((A[a][0] * p_0 + A[a][1] * p_1) + A[a][2] * p_2) + c_a       (the host: c_a = fp32(0.5 (n_a - 1) + t_a))
+ *   border:   s_a = fminf(fmaxf(s_a, lo_a), hi_a);  constant: s_a = fminf(fmaxf(s_a, lo_a - 1), hi_a + 1) (further out every corner is cval anyway; indices stay ints)
+ *   nearest:  i_a = nearbyintf(s_a) (half to even);  out = src[i], or cval when constant and some i_a is outside [lo_a, hi_a]
+ *   trilinear: i0_a = floorf(s_a), l_a = s_a - i0_a, i1_a = i0_a + 1 (border: min(i0_a + 1, hi_a)); a corner outside [lo, hi] (constant only) reads cval;
+ *              lerp(u, v, l) = (1 - l) * u + l * v along W first, then H, then D.  NaN and inf in the data go through that formula as written.
+ * Checked before the launch (-1, nothing written): records != NULL and 8-byte aligned, n_records > 0, Do, Ho, Wo > 0; -3 when the blocks exceed one grid.  Record
+ * CONTENTS cannot be seen from the host: a record whose type, mode or pad is unknown, that asks trilinear of an integer type or has lo > hi writes nothing;
+ * pointers, strides and ranges are the caller's to get right (veloxseg_amd/utils/augment.py: affine_sample checks them before the upload). */
+#define VX_AFFINE_RECORD_BYTES 144
+int vx_affine_batch(const void* records, int n_records, int Do, int Ho, int Wo, void* stream);
+
 /* ---- volume preprocessing (csrc/preprocess.hip): foreground z-score, CT clip + normalise, dataset order statistics, separable resampling -----------------
  * Reference: preprocess/normalization_MRI.py:7-12,52, preprocess/normalization_CT_PET.py:6-11,23-31,65-81, utils/inference_extern_mri.py:73-75,95.
  * Volumes are fp32 contiguous, indexed with `long`; masks / labels are uint8 / int32 / int64 / fp32 (bytes code 1 / 4 / 8 / -4, as in vx_label_chunk_count),

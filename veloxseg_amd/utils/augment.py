@@ -3,7 +3,9 @@ CropForegroundd(select_fn = x > x.min()), RandCropByPosNegLabeld and RandRotated
 (C, D, H, W) tensors that are already resident in HBM.  The reductions, the label rank-select and the resampling are HIP kernels (csrc/augment.hip);
 random draws are taken on the host from numpy's RandomState in MONAI's order.  There is no CPU fallback.
 Beyond the reference's three: RandFlipd, RandScaleIntensityd, RandShiftIntensityd, RandGaussianNoised and BatchAssembler, which applies them while ONE kernel call
-(csrc/augment_batch.hip) writes the (B, M, D, H, W) batch and its int64 labels; from_config reads train_config["augment"]."""
+(csrc/augment_batch.hip) writes the (B, M, D, H, W) batch and its int64 labels; from_config reads train_config["augment"].
+RandAffined / affine_sample / affine_matrix: rotation about all three axes, scale and translation of every sample, key and channel in ONE kernel call
+(csrc/augment_affine.hip); spatial_from_config reads train_config["spatial_augment"]."""
 import math
 
 import numpy as np
@@ -128,11 +130,15 @@ class CropForegroundd:
 
 
 class RandCropByPosNegLabeld(_Randomizable):
-    def __init__(self, keys, label_key, spatial_size, pos=1.0, neg=1.0, num_samples=1, allow_smaller=False):
+    """copy=True (default): every crop is copied out, as MONAI does.  copy=False: the crops are VIEWS of the volume (no copy, same draws, same voxels) and every
+    sample also carries `crop_start` (the window's origin in the cropped-from volume) and `crop_source_shape` (that volume's spatial shape), which
+    RandAffined(context=True) reads"""
+
+    def __init__(self, keys, label_key, spatial_size, pos=1.0, neg=1.0, num_samples=1, allow_smaller=False, copy=True):
         if pos < 0 or neg < 0 or pos + neg == 0:
             raise ValueError("pos and neg must be nonnegative and not both zero")
         self.keys, self.label_key, self.spatial_size = list(keys), label_key, list(spatial_size)
-        self.pos_ratio, self.num_samples, self.allow_smaller = pos / (pos + neg), int(num_samples), allow_smaller
+        self.pos_ratio, self.num_samples, self.allow_smaller, self.copy = pos / (pos + neg), int(num_samples), allow_smaller, bool(copy)
         self.set_random_state()
 
     def centers(self, label):
@@ -158,8 +164,10 @@ class RandCropByPosNegLabeld(_Randomizable):
             sl = tuple(slice(max(ci - p // 2, 0), min(max(ci - p // 2, 0) + p, s)) for ci, p, s in zip(c, self.spatial_size, shape))
             d = dict(data)
             for k in self.keys:
-                d[k] = data[k][(slice(None),) + sl].contiguous()
+                d[k] = data[k][(slice(None),) + sl].contiguous() if self.copy else data[k][(slice(None),) + sl]
             d["crop_center"] = c
+            if not self.copy:
+                d["crop_start"], d["crop_source_shape"] = [s.start for s in sl], list(shape)
             res.append(d)
         return res
 
@@ -534,6 +542,267 @@ def from_config(cfg, image_keys, label_key):
     return BatchAssembler(image_keys, label_key, ts)
 
 
+# ---- spatial augmentation: 3-D affine resampling of every sample, key and channel in one call (csrc/augment_affine.hip) --------------------
+# Modelled on MONAI 1.x (AffineGrid's composition, RandAffined's argument names, RandomizableTransform's draw order) and UNPINNED against MONAI itself, which is not
+# installed, like the transforms of section 25; tests/affine_ref.py restates the matrix and the draw order.
+AFFINE_RECORD_BYTES = 144
+_AFF = np.dtype([("src", "<u8"), ("dst", "<u8"), ("stride", "<i8", (3,)), ("n", "<i4", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("dtype", "<i4"), ("mode", "<i4"),
+                 ("pad", "<i4"), ("cval", "<f4"), ("A", "<f4", (9,)), ("c", "<f4", (3,)), ("unused", "<i4")])
+assert _AFF.itemsize == AFFINE_RECORD_BYTES
+_AFF_MODES = {"bilinear": 0, "trilinear": 0, "nearest": 1}
+_AFF_PADS = {"border": 0, "constant": 1, "zeros": 1}
+_AFF_INDEX_MAX = 1 << 24           # the kernel compares fp32 coordinates with (float)lo, (float)hi: indices must be exact in fp32
+
+
+def _three(v, what):
+    try:
+        out = [float(t) for t in v]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} {v!r}: three numbers") from None
+    if len(out) != 3 or not all(math.isfinite(t) for t in out):
+        raise ValueError(f"{what} {v!r}: three finite numbers")
+    return out
+
+
+def affine_matrix(rotate=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0), translate=(0.0, 0.0, 0.0)):
+    """fp64 (3, 4) matrix [A | t] of the map from CENTRED output coordinates to CENTRED source coordinates, s = A p + t, over the axes (D, H, W) = (x, y, z):
+    MONAI 1.x AffineGrid's composition without shear, R @ T @ S with R = Rx @ Ry @ Rz (angles in radians),
+        Rx = [[1, 0, 0], [0, c, -s], [0, s, c]]    Ry = [[c, 0, s], [0, 1, 0], [-s, 0, c]]    Rz = [[c, -s, 0], [s, c, 0], [0, 0, 1]]   (Rz: what vx_rotate_z does),
+    T the translation by `translate` (voxels), S = diag(scale): A = R S, t = R translate.  Modelled on MONAI 1.x, unpinned against MONAI itself."""
+    rx, ry, rz = _three(rotate, "rotate")
+    S = np.diag(_three(scale, "scale"))
+    t = np.array(_three(translate, "translate"), dtype=np.float64)
+    c, s = math.cos(rx), math.sin(rx)
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])
+    c, s = math.cos(ry), math.sin(ry)
+    Ry = np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+    c, s = math.cos(rz), math.sin(rz)
+    Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    R = Rx @ Ry @ Rz
+    return np.concatenate([R @ S, (R @ t)[:, None]], axis=1)
+
+
+def _affine_record(i, src, dst, matrix, mode, padding_mode, cval, bounds, seen):
+    """entry i -> (the fields of its record in the order of _AFF, the byte range it may read); every check of a record's contents happens here, before the upload.
+    `seen`: the matrices already checked in this call, by identity (the keys and channels of a sample share theirs)"""
+    what = f"affine_sample: entry {i}"
+    if not (isinstance(src, torch.Tensor) and src.is_cuda):
+        raise RuntimeError(f"{what}: the HIP path needs a CUDA (ROCm) tensor; there is no CPU fallback")
+    if src.dim() != 3:
+        raise ValueError(f"{what}: expected a (D, H, W) view, got {tuple(src.shape)}")
+    if mode not in _AFF_MODES:
+        raise ValueError(f"{what}: mode {mode!r} not supported (bilinear, nearest)")
+    if padding_mode not in _AFF_PADS:
+        raise ValueError(f"{what}: padding_mode {padding_mode!r} not supported (border, constant)")
+    code = label_code(src)
+    if _AFF_MODES[mode] == 0:
+        if src.dtype != torch.float32:
+            raise TypeError(f"{what}: mode {mode!r} on {src.dtype}: integer types take nearest only")
+        code = 0
+    n = [int(v) for v in src.shape]
+    if 0 in n:
+        raise ValueError(f"{what}: empty source {tuple(n)}")
+    if id(matrix) not in seen:
+        m = np.asarray(matrix, dtype=np.float64)
+        if m.shape != (3, 4) or not np.isfinite(m).all():
+            raise ValueError(f"{what}: the matrix must be a finite (3, 4) array")
+        seen[id(matrix)] = (m[:, :3].reshape(-1), m[:, 3].tolist())
+    A, t = seen[id(matrix)]
+    cval = float(cval)
+    if not math.isfinite(cval):
+        raise ValueError(f"{what}: cval {cval!r} is not finite")
+    lo, hi = ([0, 0, 0], [v - 1 for v in n]) if bounds is None else ([int(v) for v in bounds[0]], [int(v) for v in bounds[1]])
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"{what}: bounds must be (lo[3], hi[3])")
+    if any(a > b for a, b in zip(lo, hi)):
+        raise ValueError(f"{what}: bounds lo {lo} > hi {hi}")
+    if any(abs(v) >= _AFF_INDEX_MAX for v in lo + hi + n):
+        raise ValueError(f"{what}: extents / bounds beyond 2^24 are not supported")
+    # the whole range [lo, hi] must lie inside the storage the view points into, and the destination must not overlap it
+    st, item = list(src.stride()), src.element_size()
+    if any(abs(v) > _INT_MAX for v in st):
+        raise ValueError(f"{what}: strides {st} beyond 32 bits are not supported")
+    first = src.storage_offset() + sum(min(a * s, b * s) for a, b, s in zip(lo, hi, st))
+    last = src.storage_offset() + sum(max(a * s, b * s) for a, b, s in zip(lo, hi, st))
+    if first < 0 or (last + 1) * item > src.untyped_storage().nbytes():
+        raise ValueError(f"{what}: bounds lo {lo}, hi {hi} reach outside the memory the view belongs to")
+    if not (isinstance(dst, torch.Tensor) and dst.is_cuda and dst.is_contiguous() and dst.dtype == src.dtype and dst.device == src.device):
+        raise ValueError(f"{what}: the destination must be a contiguous {src.dtype} tensor on {src.device}")
+    base = src.data_ptr() - src.storage_offset() * item
+    c = [0.5 * (n[a] - 1) + t[a] for a in range(3)]                   # formed in fp64; the table rounds it (and A) to fp32 once
+    return ((src.data_ptr(), dst.data_ptr(), st, n, lo, hi, code, _AFF_MODES[mode], _AFF_PADS[padding_mode], cval, A, c, 0),
+            (base + first * item, base + (last + 1) * item))
+
+
+def _affine_pack(entries, out_size, out=None):
+    """every check of affine_sample, then -> (the record table as a host uint8 tensor, the destinations, out_size); nothing touches the GPU but the allocation"""
+    entries = [tuple(e) for e in entries]
+    if not entries:
+        raise ValueError("affine_sample: no entries")
+    out_size = tuple(int(v) for v in out_size)
+    if len(out_size) != 3 or any(v <= 0 or v >= _AFF_INDEX_MAX for v in out_size):
+        raise ValueError(f"affine_sample: out_size {out_size!r} must be three positive extents")
+    for i, e in enumerate(entries):
+        if len(e) not in (5, 6):
+            raise ValueError(f"affine_sample: entry {i} has {len(e)} fields (source, matrix, mode, padding_mode, cval[, bounds])")
+        if not (isinstance(e[0], torch.Tensor) and e[0].is_cuda):
+            raise RuntimeError(f"affine_sample: entry {i}: the HIP path needs a CUDA (ROCm) tensor; there is no CPU fallback")
+    if out is None:
+        out = [torch.empty(out_size, dtype=e[0].dtype, device=e[0].device) for e in entries]
+    out = list(out)
+    if len(out) != len(entries) or any(tuple(o.shape) != out_size for o in out):
+        raise ValueError(f"affine_sample: `out` must hold one {out_size} tensor per entry")
+    seen = {}
+    recs = [_affine_record(i, e[0], o, e[1], e[2], e[3], e[4], e[5] if len(e) == 6 else None, seen) for i, (e, o) in enumerate(zip(entries, out))]
+    tab = np.zeros(len(entries), dtype=_AFF)
+    for f, name in enumerate(_AFF.names):                             # one assignment per field, not per record
+        tab[name] = [r[0][f] for r in recs]
+    # no destination may overlap what ANY record reads (the blocks of all records run side by side)
+    reads = np.array([r[1] for r in recs], dtype=np.uint64)
+    writes = np.array([(o.data_ptr(), o.data_ptr() + o.numel() * o.element_size()) for o in out], dtype=np.uint64)
+    clash = (writes[:, None, 0] < reads[None, :, 1]) & (reads[None, :, 0] < writes[:, None, 1])
+    if clash.any():
+        i, j = (int(v[0]) for v in np.nonzero(clash))
+        raise ValueError(f"affine_sample: the destination of entry {i} overlaps the source of entry {j}: source and destination alias")
+    return torch.from_numpy(tab.view(np.uint8).reshape(-1)), out, out_size
+
+
+def affine_sample(entries, out_size, out=None):
+    """entries: [(source (D, H, W) CUDA view, (3, 4) matrix of affine_matrix, mode, padding_mode, cval[, bounds])] -> one (Do, Ho, Wo) tensor of the source's dtype per
+    entry, out_size = (Do, Ho, Wo) for all of them, in ONE table, ONE upload, ONE call of vx_affine_batch (the rule: include/veloxseg_hip.h).  mode "bilinear"
+    (float32 only) or "nearest"; padding_mode "border" or "constant" (cval outside); bounds = (lo[3], hi[3]), the valid index range in the view's coordinates (default
+    0 .. n-1; -start .. parent-1-start lets a crop view read its parent).  Sources may be any strided views (no .contiguous()).  `out`: the destinations to write
+    (contiguous, same dtype), else they are allocated.  Everything is checked before any GPU work; there is no CPU fallback."""
+    table, out, out_size = _affine_pack(entries, out_size, out)
+    table = table.to(out[0].device)
+    H.call("vx_affine_batch", table.data_ptr(), len(out), *out_size, H.stream_ptr())
+    return out
+
+
+def _axis_ranges(v, what):
+    """MONAI's reading of rotate_range / translate_range / scale_range: None -> no range; a sequence of up to three entries, one per axis (D, H, W), missing axes 0;
+    an entry that is a number r means (-|r|, |r|), a pair means (min, max); a bare number is the one-entry sequence (the FIRST axis), as MONAI's ensure_tuple reads it"""
+    if v is None:
+        return [(0.0, 0.0)] * 3
+    seq = [v] if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) else list(v)
+    if len(seq) > 3:
+        raise ValueError(f"{what} {v!r}: at most three entries (D, H, W)")
+    return [_range(e, what) for e in seq] + [(0.0, 0.0)] * (3 - len(seq))
+
+
+class RandAffined(_Randomizable):
+    """MONAI RandAffined(keys, prob, rotate_range, scale_range, translate_range, spatial_size, mode, padding_mode) without shear, plus cval (the value outside under
+    padding_mode="constant") and context (below).  Angles in radians about (D, H, W) = (x, y, z), translations in voxels, the scale is 1 + its draw; the matrix is
+    affine_matrix(rotate, scale, translate), the map from centred output to centred source coordinates.
+    Draw order (modelled on MONAI 1.x, unpinned against MONAI itself; tests/affine_ref.py restates it): one RandomState; every sample draws R.rand() < prob FIRST and
+    its parameters ONLY IF that fires: three rotation uniforms (x, y, z), then three translation uniforms, then three scale uniforms, each drawn even where its range
+    is zero; one draw set per sample, shared by its keys.
+    Called on a dict or on a LIST of dicts (Compose hands it the list whole: takes_list), it resamples every fired sample, key and channel in ONE call of
+    vx_affine_batch, straight from the tensors it is given (views are fine, nothing is copied first).  A sample that does not fire keeps its tensors and costs no
+    launch (unless spatial_size differs from its shape: then it is resampled with the identity).  mode: one per key or one for all ("bilinear" float32 only,
+    "nearest"); outputs keep the dtype of their source.  context=True: the samples are crop views (RandCropByPosNegLabeld(copy=False)) and the sampler may read the
+    crop's parent outside the window, so a rotated patch sees the volume's real neighbours instead of clamped border values; needs the crop's `crop_start` and
+    `crop_source_shape` in every sample."""
+    takes_list = True
+
+    def __init__(self, keys, prob=0.1, rotate_range=None, scale_range=None, translate_range=None, spatial_size=None, mode="bilinear", padding_mode="border", cval=0.0,
+                 context=False):
+        self.keys, self.prob = list(keys), _prob(prob)
+        self.rotate_range, self.translate_range = _axis_ranges(rotate_range, "rotate_range"), _axis_ranges(translate_range, "translate_range")
+        self.scale_range = _axis_ranges(scale_range, "scale_range")
+        self.spatial_size = None if spatial_size is None else tuple(int(v) for v in spatial_size)
+        if self.spatial_size is not None and (len(self.spatial_size) != 3 or min(self.spatial_size) <= 0):
+            raise ValueError(f"spatial_size {spatial_size!r}: three positive extents")
+        self.mode = [mode] * len(self.keys) if isinstance(mode, str) else list(mode)
+        if len(self.mode) != len(self.keys):
+            raise ValueError("mode must have one entry per key")
+        for m in self.mode:
+            if m not in _AFF_MODES:
+                raise ValueError(f"mode {m!r} not supported (bilinear, nearest)")
+        if padding_mode not in _AFF_PADS:
+            raise ValueError(f"padding_mode {padding_mode!r} not supported (border, constant)")
+        self.padding_mode, self.cval, self.context = padding_mode, float(cval), bool(context)
+        self.set_random_state()
+
+    def draw(self):
+        """-> None (the sample does not fire) or (rotate[3], translate[3], scale[3])"""
+        if not self.R.rand() < self.prob:
+            return None
+        rot = [float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.rotate_range]
+        tra = [float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.translate_range]
+        sca = [1.0 + float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.scale_range]
+        return rot, tra, sca
+
+    def __call__(self, data):
+        if not isinstance(data, list):
+            return self([data])[0]
+        outs, entries, slots, out_size = [], [], [], self.spatial_size
+        for i, d in enumerate(data):
+            params = self.draw()
+            out = dict(d)
+            outs.append(out)
+            if params is None and self.spatial_size is None:
+                continue
+            for k in self.keys:
+                _need_cuda(d[k], f"RandAffined[{k!r}]")
+            shapes = {tuple(d[k].shape[1:]) for k in self.keys}
+            if len(shapes) != 1:
+                raise ValueError(f"RandAffined: sample {i}: keys of different spatial shapes {sorted(shapes)}")
+            shape = shapes.pop()
+            size = self.spatial_size or shape
+            if params is None and size == shape:
+                continue
+            if out_size is None:
+                out_size = size
+            if size != out_size:
+                raise ValueError(f"RandAffined: sample {i} has the patch shape {shape}, the call {out_size}: set spatial_size")
+            bounds = None
+            if self.context:
+                if "crop_start" not in d or "crop_source_shape" not in d:
+                    raise ValueError("RandAffined(context=True) needs `crop_start` and `crop_source_shape` in every sample: crop with RandCropByPosNegLabeld(copy=False)")
+                start, parent = [int(v) for v in d["crop_start"]], [int(v) for v in d["crop_source_shape"]]
+                bounds = ([-s for s in start], [p - 1 - s for p, s in zip(parent, start)])
+            m = affine_matrix() if params is None else affine_matrix(rotate=params[0], scale=params[2], translate=params[1])
+            for k, mode in zip(self.keys, self.mode):
+                t = d[k]
+                for ch in range(t.shape[0]):
+                    entries.append((t[ch], m, mode, self.padding_mode, self.cval, bounds) if bounds is not None else (t[ch], m, mode, self.padding_mode, self.cval))
+                slots.append((out, k, t.shape[0], t.dtype, t.device))
+        if not entries:
+            return outs
+        dests = [torch.empty((c,) + out_size, dtype=dt, device=dev) for _, _, c, dt, dev in slots]
+        affine_sample(entries, out_size, out=[v[ch] for v in dests for ch in range(v.shape[0])])
+        for (out, k, _, _, _), v in zip(slots, dests):
+            out[k] = v
+        return outs
+
+
+_SPATIAL_KEYS = ("rotate_degrees", "scale", "translate", "prob", "padding_mode", "context")
+
+
+def spatial_from_config(cfg, keys, modes):
+    """train_config["spatial_augment"] -> RandAffined.  Keys (all optional; an unknown key raises ValueError): rotate_degrees (a number: that range about each of the
+    three axes; or three values, about D, H, W), scale (a number or three: the scale is 1 + U(-v, v) per axis), translate (voxels, a number or three), prob (default
+    0.5, the chain's rotation probability), padding_mode ("border" default, or "constant"), context (default False: with it the crop hands views over and the
+    sampler reads the volume around the patch)."""
+    if not isinstance(cfg, dict):
+        raise ValueError(f"spatial_augment config must be a dict, got {type(cfg).__name__}")
+    unknown = sorted(set(cfg) - set(_SPATIAL_KEYS))
+    if unknown:
+        raise ValueError(f"spatial_augment config: unknown keys {unknown} (known: {', '.join(_SPATIAL_KEYS)})")
+
+    def per_axis(v, what, f=float):
+        if v is None:
+            return None
+        vals = [v] * 3 if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) else list(v)
+        if len(vals) != 3:
+            raise ValueError(f"spatial_augment config: {what} {v!r}: a number or three values")
+        return [f(t) for t in vals]
+    return RandAffined(keys, prob=cfg.get("prob", 0.5), rotate_range=per_axis(cfg.get("rotate_degrees"), "rotate_degrees", rotation_range_from_degrees),
+                       scale_range=per_axis(cfg.get("scale"), "scale"), translate_range=per_axis(cfg.get("translate"), "translate"), mode=modes,
+                       padding_mode=cfg.get("padding_mode", "border"), context=bool(cfg.get("context", False)))
+
+
 class Compose:
     def __init__(self, transforms):
         self.transforms = list(transforms)
@@ -547,5 +816,6 @@ class Compose:
 
     def __call__(self, data):
         for t in self.transforms:
-            data = [t(d) for d in data] if isinstance(data, list) and not isinstance(t, RandRotated) else t(data)
+            whole = isinstance(t, RandRotated) or getattr(t, "takes_list", False)          # takes_list: the transform wants the list of samples in one call
+            data = [t(d) for d in data] if isinstance(data, list) and not whole else t(data)
         return data

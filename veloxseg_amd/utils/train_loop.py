@@ -53,19 +53,27 @@ class SyntheticVolumes:
     """whole synthetic cases (padded background + a foreground body + lesion blobs) pushed through the reference's transform chain on the GPU
     (utils/augment.py: CropForegroundd -> RandCropByPosNegLabeld(num_samples) -> RandRotated): `batch` patches per step, batch / num_samples cases per step.
     augment: None (the chain above, batches put together with cat / stack / .long()) or the train_config["augment"] dict of utils.augment.from_config: mirror, scale,
-    shift and noise drawn per patch and applied while ONE kernel call writes the batch (utils.augment.BatchAssembler)"""
+    shift and noise drawn per patch and applied while ONE kernel call writes the batch (utils.augment.BatchAssembler).
+    spatial: None (the chain above) or the train_config["spatial_augment"] dict of utils.augment.spatial_from_config: RandAffined (rotation about all three axes,
+    scale, translation; ONE kernel call for all patches of a case) takes the place of the chain's RandRotated; with its `context` on, the crop hands over views
+    (copy=False) and the sampler reads the volume around each patch"""
 
-    def __init__(self, model_cfg, batch, steps, device, volume=(160, 160, 144), num_samples=2, seed=12345, rotate_degrees=15.0, augment=None):
+    def __init__(self, model_cfg, batch, steps, device, volume=(160, 160, 144), num_samples=2, seed=12345, rotate_degrees=15.0, augment=None, spatial=None):
         from . import augment as A
         if batch % num_samples:
             raise ValueError("batch must be a multiple of num_samples")
         self.cfg, self.batch, self.steps, self.device, self.volume, self.seed, self.ns = model_cfg, batch, steps, device, tuple(volume), seed, num_samples
         self.M = sum(model_cfg["in_ch"])
         self.keys = [f"img{m}" for m in range(self.M)] + ["seg"]
+        if spatial is None:
+            crop_kw, deform = {}, A.RandRotated(self.keys, range_z=A.rotation_range_from_degrees(rotate_degrees), mode=A.image_label_modes(self.M), prob=0.5)
+        else:
+            deform = A.spatial_from_config(spatial, self.keys, A.image_label_modes(self.M))
+            crop_kw = {"copy": False} if deform.context else {}
         self.pipe = A.Compose([
             A.CropForegroundd(self.keys, "img0"),
-            A.RandCropByPosNegLabeld(self.keys, "seg", model_cfg["input_size"], pos=1, neg=1, num_samples=num_samples),
-            A.RandRotated(self.keys, range_z=A.rotation_range_from_degrees(rotate_degrees), mode=A.image_label_modes(self.M), prob=0.5),
+            A.RandCropByPosNegLabeld(self.keys, "seg", model_cfg["input_size"], pos=1, neg=1, num_samples=num_samples, **crop_kw),
+            deform,
         ]).set_random_state(seed)
         # its own seed sequence: the assembler's transforms must not repeat the streams of the chain above
         self.assembler = None if augment is None else A.from_config(augment, self.keys[:-1], "seg").set_random_state([int(seed) & 0xFFFFFFFF, 0xA6])
@@ -138,9 +146,11 @@ def run_train(args, train_config, model_config, train_loader: Optional[Iterable]
     rank = dist.get_rank() if ddp else 0
     if train_loader is None:
         # every rank draws its OWN synthetic stream (seed + rank): data parallelism must add data, not replicate the same batch on every GPU
-        # --augment with train_config["augment"] set: mirror / intensity / noise on top of the chain (utils.augment.from_config); without the key, the chain alone
+        # --augment with train_config["augment"] set: mirror / intensity / noise on top of the chain (utils.augment.from_config); without the key, the chain alone;
+        # with train_config["spatial_augment"] set: RandAffined in the place of the chain's z-rotation (utils.augment.spatial_from_config)
         if getattr(args, "augment", False):
-            train_loader = SyntheticVolumes(mcfg, batch, getattr(args, "synthetic_steps", 4), device, seed=12345 + rank, augment=train_config.get("augment"))
+            train_loader = SyntheticVolumes(mcfg, batch, getattr(args, "synthetic_steps", 4), device, seed=12345 + rank, augment=train_config.get("augment"),
+                                            spatial=train_config.get("spatial_augment"))
         else:
             train_loader = SyntheticPatches(mcfg, batch, getattr(args, "synthetic_steps", 4), device, seed=12345 + rank)
     # engine buffers from the configuration, not from a pulled batch (that would consume one batch of a one-shot iterable and spin up an extra
