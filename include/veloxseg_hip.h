@@ -608,7 +608,8 @@ int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float co
  *   byte  36  int32   b: destination sample, 0 <= b < B
  *   byte  40  int32   c: destination channel, 0 <= c < M (image) or VX_AUG_LABEL = -1 (label)
  *   byte  44  int32   flip mask, bit a = axis a of (D, H, W) mirrored: out[d, h, w] = src[D-1-d | d, H-1-h | h, W-1-w | w]
- *   byte  48  int32   number of pointwise steps, 0..VX_AUG_MAX_STEPS (images only); bytes 52..63 unused
+ *   byte  48  int32   number of pointwise steps, 0..VX_AUG_MAX_STEPS (images only); bytes 52..55 unused
+ *   byte  56  uint64  device address of the statistics table that ops 4..6 read (section below), or 0: none -- what every table without such a step holds
  *   byte  64  8 steps of 16 bytes { uint32 op, float a, float b, uint32 key }, applied in order, each operation rounded to fp32 on its own (nothing is contracted):
  *               op & 15 = 1  mul    t = t * a
  *               op & 15 = 2  add    t = t + a
@@ -625,6 +626,43 @@ int vx_rotate_z(const float* x, float* out, int C, int D, int H, int W, float co
 #define VX_AUG_LABEL (-1)
 #define VX_AUG_NOISE_STREAM 0x564158475541ull      /* "AUGXAV": far above every dropout site id (those count up from 1, functional.new_dropout_site) */
 int vx_augment_batch(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream);
+
+/* ---- blur, gamma and fixed-mean contrast (csrc/augment_blur.hip, csrc/augment_stats.hip) ----
+ * Three more ops of the step program above, known to vx_augment_batch_ext ONLY (vx_augment_batch skips them; the host picks _ext for a table that holds one).  Each
+ * reads a slot of the record's statistics table (byte 56), an array of VX_AUG_STAT_BYTES-byte slots { float min, max, mean, std; double S1, S2 }; every operation is
+ * rounded to fp32 on its own:
+ *               op & 15 = 4  contrast  t = ((t - mean) * a) + mean, then fminf(fmaxf(t, min), max) when b != 0;                                slot = key
+ *               op & 15 = 5  gamma     r = max - min;  t = powf((t - min) / (r + 1e-7f), a) * r + min;                                          slot = key
+ *               op & 15 = 6  retain    t = (t - mean2) / (std2 + 1e-8f) * std1 + mean1;                   slot 2 (mean2, std2) = key, slot 1 (mean1, std1) = op >> 8
+ *             (op >> 4) & 7 is, as for the noise, the mask of the flips that follow the step: the frame its statistic is taken in.
+ * vx_augment_stats fills slots.  A job is VX_AUG_STAT_JOB_BYTES bytes { int32 record index, int32 upto, int32 slot, int32 frame }: steps 0 .. upto-1 of that record's
+ * program are evaluated on every voxel (ops 4..6 among them read slots that an EARLIER call filled), in the frame `frame` (the mask of the flips between it and the
+ * output: voxel f of the frame is source voxel f mirrored by flip ^ frame, and a noise step finds its element under its own mask ^ frame), and
+ *   min, max exact fp32 (fminf / fmaxf: a NaN voxel is skipped);  S1 = sum x, S2 = sum x^2 in fp64 from the fp32 values (a NaN or inf voxel makes mean and std NaN);
+ *   mean = fp32(S1 / V);  std = fp32(sqrt(max((S2 - S1 * S1 / V) / (V - 1), 0))) in fp64, in that order (torch's unbiased std; V = 1 gives NaN)
+ * go to slot `slot` of the record's table.  Two launches per call, whatever n_jobs: chunks of VX_AUG_STAT_CHUNK voxels -> partials (lane t of a chunk takes voxels
+ * i * 256 + t, i ascending, then a fixed tree), then one block per job folds its partials (lane t takes partials t, t + 256, ..., then the tree).  The mapping depends on
+ * V = D*H*W only, so a slot has the same bits in every run and whichever other jobs share the call.  No workgroup waits for another; nothing visits the host.
+ * `partials`: device scratch of at least n_jobs * ceil(V / VX_AUG_STAT_CHUNK) * VX_AUG_STAT_PARTIAL_BYTES bytes.  Checked before any launch (-1, nothing written):
+ * pointers non-null and 8-byte aligned, n_records, n_jobs > 0, positive extents, the size of `partials`, the grid.  A job whose record index is out of range, whose
+ * record is no fp32 image or has no table, or whose slot is negative writes nothing; slot numbers and table sizes are the caller's to get right. */
+#define VX_AUG_STAT_BYTES 32
+#define VX_AUG_STAT_JOB_BYTES 16
+#define VX_AUG_STAT_PARTIAL_BYTES 24
+#define VX_AUG_STAT_CHUNK 4096
+int vx_augment_batch_ext(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream);
+int vx_augment_stats(const void* records, int n_records, const void* jobs, int n_jobs, void* partials, long partial_bytes, int D, int H, int W, void* stream);
+/* Separable blur with zero padding.  `records`: DEVICE table of n_records records of VX_BLUR_RECORD_BYTES bytes, one per (D, H, W) channel:
+ *   byte   0  uint64     source device pointer (fp32; a strided view is fine)        byte   8  uint64  destination: a contiguous (D, H, W) fp32 volume, not the source
+ *   byte  16  int64[3]   strides of the source over (D, H, W), in elements
+ *   byte  40  int32[3]   tail of the weight vector of axis D, H, W: 0 <= tail <= VX_BLUR_MAX_TAIL (a record outside that range writes nothing); byte 52 unused
+ *   byte  56  float[3][VX_BLUR_MAX_TAIL + 1]  w_0 .. w_tail of axis D, H, W: the centre and ONE half of the symmetric vector;  bytes 260..271 unused
+ * Passes W, H, D, each output rounded to fp32 before the next; in a pass y = w_0 x_0 + sum_{k = 1 .. tail} w_k (x_-k + x_+k), k ascending, the pair added first, x = 0
+ * outside the patch.  `tmp`: n_records * D*H*W floats of device scratch.  Three launches per call, whatever n_records.  Checked before any launch (-1, nothing
+ * written): pointers, n_records > 0, positive extents, alignment (table 8 bytes); -3 when the blocks exceed one grid. */
+#define VX_BLUR_RECORD_BYTES 272
+#define VX_BLUR_MAX_TAIL 16
+int vx_blur_batch(const void* records, int n_records, float* tmp, int D, int H, int W, void* stream);
 
 /* ---- spatial augmentation (csrc/augment_affine.hip): 3-D affine resampling of any number of volumes in ONE launch ----
  * `records` is a DEVICE table of n_records records of VX_AFFINE_RECORD_BYTES bytes; one record = one output volume (one channel of one key of one sample):

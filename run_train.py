@@ -30,7 +30,7 @@ if __name__ == "__main__":
     parser.add_argument("--model_index", type=str, default=None, help="Markdown index of the model")
     parser.add_argument("--select_modal", type=int, default=None)
     parser.add_argument("--synthetic", type=int, default=8, dest="synthetic_steps", help="synthetic batches per epoch")
-    parser.add_argument("--augment", action="store_true", help="synthetic whole cases through the GPU transform chain (crop foreground, pos/neg crop, z-rotation) instead of ready-made patches; train_config[\"augment\"] (flip_axes, flip_prob, scale, scale_prob, shift, shift_prob, noise_std, noise_prob) adds mirror, intensity and noise to the batch assembly; train_config[\"spatial_augment\"] (rotate_degrees, scale, translate, prob, padding_mode, context) puts a 3-D affine resampling (rotation about all three axes, zoom, shift; one kernel call per case) in the place of the z-rotation")
+    parser.add_argument("--augment", action="store_true", help="synthetic whole cases through the GPU transform chain (crop foreground, pos/neg crop, z-rotation) instead of ready-made patches; train_config[\"augment\"] (flip_axes, flip_prob, scale, scale_prob, shift, shift_prob, noise_std, noise_prob, blur_sigma, blur_prob, contrast_factors, contrast_prob, contrast_preserve_range, gamma_range, gamma_prob, gamma_invert, gamma_retain_stats) adds mirror, intensity, noise, Gaussian blur, fixed-mean contrast and gamma to the batch assembly; train_config[\"spatial_augment\"] (rotate_degrees, scale, translate, prob, padding_mode, context) puts a 3-D affine resampling (rotation about all three axes, zoom, shift; one kernel call per case) in the place of the z-rotation")
     parser.add_argument("--data_module", type=str, default=None, help="python module with build_loaders(args, train_config, model_config)")
     parser.add_argument("--save_path", type=str, default=None, help="checkpoint directory (default ./checkpoints/<date>_<dataset>)")
     parser.add_argument("--graph", action="store_true", dest="use_graph", help="capture the training step once and replay it as a launch tape (csrc/tape.hip: ~2 ms of host time per step instead of ~10 ms; falls back to eager launches if the capture cannot be verified)")

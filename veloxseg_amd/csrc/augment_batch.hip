@@ -4,54 +4,7 @@
 // ONE record, so the record is block-uniform (blockIdx only) and its fields, the step program included, come through scalar loads; the lanes walk the patch in flat
 // order, four voxels each when W % 4 == 0 (16-byte stores always; 16-byte loads when the source row is contiguous and aligned, four scalar loads otherwise), one
 // voxel each when it is not.  No operation of the pointwise program is contracted with another: the fused result has the bits of the transforms applied one by one.
-#include "vx_common.h"
-#include "../../include/veloxseg_hip.h"
-
-struct VxAugStep { uint32_t op; float a, b; uint32_t key; };
-struct VxAugRecord {
-    const void* src;
-    long stride[3];
-    int dtype, b, c, flip;
-    int n_steps, pad[3];
-    VxAugStep step[VX_AUG_MAX_STEPS];
-};
-static_assert(sizeof(VxAugRecord) == VX_AUG_RECORD_BYTES, "record layout drifted from the header");
-
-// every product and sum of the program is rounded on its own (hipcc contracts a * b + c under plain -O3 unless told otherwise)
-__device__ __forceinline__ float vx_aug_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float vx_aug_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-// Box-Muller on the 24-bit uniforms of the dropout code: u1 in (0, 1] (the logarithm's argument), u2 in [0, 1); precise library functions
-__device__ __forceinline__ void vx_aug_normal_pair(uint32_t ra, uint32_t rb, float& n0, float& n1) {
-    const float u1 = (float)((ra >> 8) + 1u) * (1.0f / 16777216.0f);
-    const float two_u2 = (float)(rb >> 8) * (1.0f / 8388608.0f);          // 2 * u2, exact
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(two_u2, &sn, &cs);
-    n0 = vx_aug_mul(rad, cs);
-    n1 = vx_aug_mul(rad, sn);
-}
-// the normals of elements e0 .. e0 + 3, e0 % 4 == 0: one Philox call
-__device__ __forceinline__ void vx_aug_normal4(uint32_t key, long e0, float (&n)[4]) {
-    uint32_t r[4];
-    vx_philox4((uint64_t)key, VX_AUG_NOISE_STREAM, (uint64_t)e0 >> 2, r);
-    vx_aug_normal_pair(r[0], r[1], n[0], n[1]);
-    vx_aug_normal_pair(r[2], r[3], n[2], n[3]);
-}
-__device__ __forceinline__ float vx_aug_normal1(uint32_t key, long e) {
-    uint32_t r[4];
-    vx_philox4((uint64_t)key, VX_AUG_NOISE_STREAM, (uint64_t)e >> 2, r);
-    const bool hi = (e & 2) != 0;
-    float n0, n1;
-    vx_aug_normal_pair(hi ? r[2] : r[0], hi ? r[3] : r[1], n0, n1);
-    return (e & 1) ? n1 : n0;
-}
+#include "augment_steps.h"
 
 // four consecutive source elements p[0], p[s], p[2s], p[3s]: ONE 16-byte (4 x sizeof(T) for the narrower / wider types) access when they are adjacent and aligned.
 // Sources live in device memory: the loads go through global pointers (a pointer read from the table is generic to the compiler, which would emit flat loads).
@@ -68,22 +21,6 @@ __device__ __forceinline__ void vx_aug_load4(const T* __restrict__ p, long s, T 
         const VX_AUG_GLOBAL T* g = (const VX_AUG_GLOBAL T*)p;
 #pragma unroll
         for (int k = 0; k < 4; ++k) t[k] = g[k * s];
-    }
-}
-
-// (d, h, w) of the flat patch index v: the index is `long`, but a patch below 2^31 voxels (uniform test) takes 32-bit divisions instead of the software sequence
-// of a 64-bit one (measured at B 4, M 2, 128^3: 39.9 -> 39.3 us, so the divisions are not what bounds the pass)
-__device__ __forceinline__ void vx_aug_coords(long v, long V, int H, int W, int& d, int& h, int& w) {
-    if (V <= 0x7fffffffL) {
-        const unsigned u = (unsigned)v, row = u / (unsigned)W;
-        w = (int)(u - row * (unsigned)W);
-        d = (int)(row / (unsigned)H);
-        h = (int)(row - (unsigned)d * (unsigned)H);
-    } else {
-        const long row = v / W;
-        w = (int)(v - row * W);
-        d = (int)(row / H);
-        h = (int)(row - (long)d * H);
     }
 }
 
@@ -142,6 +79,38 @@ __global__ void __launch_bounds__(256) vx_augment_image_k(const VxAugRecord* __r
     else o[0] = t[0];
 }
 
+// The same pass with the statistics ops 4..6, through the step function the statistics pass shares (augment_steps.h).  A kernel of its own:
+// the kernel above keeps the code it had before these ops existed (folding them into it cost the noise program 3 % at B 4, M 2, 128^3: 51.3 -> 52.8 us).
+template <bool QUAD>
+__global__ void __launch_bounds__(256) vx_augment_image_ext_k(const VxAugRecord* __restrict__ recs, float* __restrict__ out, int B, int M, int D, int H, int W, long items, int bpr) {
+    const VxAugRecord* __restrict__ R = recs + (blockIdx.x / (unsigned)bpr);
+    const long it = (long)(blockIdx.x % (unsigned)bpr) * 256 + threadIdx.x;
+    const int b = R->b, c = R->c, flip = R->flip;
+    if (R->dtype != 0 || b < 0 || b >= B || c < 0 || c >= M || it >= items) return;
+    const long V = (long)D * H * W;
+    const long v = QUAD ? it * 4 : it;
+    int d, h, w;
+    vx_aug_coords(v, V, H, W, d, h, w);
+    constexpr int N = QUAD ? 4 : 1;
+    const int sd = (flip & 1) ? D - 1 - d : d, sh = (flip & 2) ? H - 1 - h : h, sw = (flip & 4) ? W - N - w : w;
+    const long s2 = R->stride[2];
+    const float* __restrict__ p = static_cast<const float*>(R->src) + sd * R->stride[0] + sh * R->stride[1] + sw * s2;
+    float t[N];
+    if (QUAD) {
+        float q[4];
+        vx_aug_load4<float>(p, s2, q);
+#pragma unroll
+        for (int k = 0; k < N; ++k) t[k] = (flip & 4) ? q[3 - k] : q[k];        // a W-flip reads the mirrored four voxels and reverses them in registers
+    } else {
+        t[0] = ((const VX_AUG_GLOBAL float*)p)[0];
+    }
+    const int ns = min(max(R->n_steps, 0), VX_AUG_MAX_STEPS);
+    vx_aug_run_steps<N, true>(R, ns, t, d, h, w, D, H, W, V, 0);
+    float* __restrict__ o = out + ((long)b * M + c) * V + v;
+    if (QUAD) *reinterpret_cast<float4*>(o) = make_float4(t[0], t[N > 1 ? 1 : 0], t[N > 2 ? 2 : 0], t[N > 3 ? 3 : 0]);
+    else o[0] = t[0];
+}
+
 template <typename T, bool QUAD>
 __device__ __forceinline__ void vx_aug_label_item(const VxAugRecord* __restrict__ R, long long* __restrict__ o, int sd, int sh, int sw, bool wflip) {
     const long s2 = R->stride[2];
@@ -179,27 +148,33 @@ __global__ void __launch_bounds__(256) vx_augment_label_k(const VxAugRecord* __r
     else if (ty == -4) vx_aug_label_item<float, QUAD>(R, o, sd, sh, sw, wf);
 }
 
-extern "C" int vx_augment_batch(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream) {
-    VX_REQUIRE(records, "vx_augment_batch: null pointer (records)");
-    VX_REQUIRE(n_image >= 0 && n_label >= 0 && (long)n_image + n_label > 0, "vx_augment_batch: no records (n_image %d, n_label %d)", n_image, n_label);
-    VX_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "vx_augment_batch: non-positive extent (B %d, D %d, H %d, W %d)", B, D, H, W);
-    VX_REQUIRE(M >= 1 && M <= 64, "vx_augment_batch: M %d outside 1..64", M);
-    VX_REQUIRE(label_bytes == 8, "vx_augment_batch: label width %d bytes not supported (the label batch is int64: 8)", label_bytes);
-    VX_REQUIRE(n_image == 0 || x_out, "vx_augment_batch: null pointer (x_out with %d image records)", n_image);
-    VX_REQUIRE(n_label == 0 || y_out, "vx_augment_batch: null pointer (y_out with %d label records)", n_label);
+template <bool EXT>
+static int vx_augment_batch_impl(const char* who, const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream) {
+    VX_REQUIRE(records, "%s: null pointer (records)", who);
+    VX_REQUIRE(n_image >= 0 && n_label >= 0 && (long)n_image + n_label > 0, "%s: no records (n_image %d, n_label %d)", who, n_image, n_label);
+    VX_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "%s: non-positive extent (B %d, D %d, H %d, W %d)", who, B, D, H, W);
+    VX_REQUIRE(M >= 1 && M <= 64, "%s: M %d outside 1..64", who, M);
+    VX_REQUIRE(label_bytes == 8, "%s: label width %d bytes not supported (the label batch is int64: 8)", who, label_bytes);
+    VX_REQUIRE(n_image == 0 || x_out, "%s: null pointer (x_out with %d image records)", who, n_image);
+    VX_REQUIRE(n_label == 0 || y_out, "%s: null pointer (y_out with %d label records)", who, n_label);
     VX_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0 && (reinterpret_cast<uintptr_t>(x_out) & 15) == 0 && (reinterpret_cast<uintptr_t>(y_out) & 15) == 0,
-               "vx_augment_batch: misaligned table (8 bytes) or output (16 bytes)");
+               "%s: misaligned table (8 bytes) or output (16 bytes)", who);
     const long V = (long)D * H * W;
     const bool quad = (W & 3) == 0;
     const long items = quad ? V / 4 : V;
     const long bpr = (items + 255) / 256;
-    VX_REQUIRE(bpr * (long)(n_image > n_label ? n_image : n_label) <= 0x7fffffffL, "vx_augment_batch: %ld blocks per record x %d records exceed one grid", bpr, n_image > n_label ? n_image : n_label);
+    VX_REQUIRE(bpr * (long)(n_image > n_label ? n_image : n_label) <= 0x7fffffffL, "%s: %ld blocks per record x %d records exceed one grid", who, bpr, n_image > n_label ? n_image : n_label);
     hipStream_t st = (hipStream_t)stream;
     const VxAugRecord* recs = static_cast<const VxAugRecord*>(records);
     if (n_image > 0) {
         const dim3 g((unsigned)(bpr * n_image)), blk(256);
-        if (quad) vx_augment_image_k<true><<<g, blk, 0, st>>>(recs, x_out, B, M, D, H, W, items, (int)bpr);
-        else vx_augment_image_k<false><<<g, blk, 0, st>>>(recs, x_out, B, M, D, H, W, items, (int)bpr);
+        if (EXT) {
+            if (quad) vx_augment_image_ext_k<true><<<g, blk, 0, st>>>(recs, x_out, B, M, D, H, W, items, (int)bpr);
+            else vx_augment_image_ext_k<false><<<g, blk, 0, st>>>(recs, x_out, B, M, D, H, W, items, (int)bpr);
+        } else {
+            if (quad) vx_augment_image_k<true><<<g, blk, 0, st>>>(recs, x_out, B, M, D, H, W, items, (int)bpr);
+            else vx_augment_image_k<false><<<g, blk, 0, st>>>(recs, x_out, B, M, D, H, W, items, (int)bpr);
+        }
         VX_LAUNCH_CHECK("vx_augment_batch (images)");
     }
     if (n_label > 0) {
@@ -209,4 +184,12 @@ extern "C" int vx_augment_batch(const void* records, int n_image, int n_label, f
         VX_LAUNCH_CHECK("vx_augment_batch (labels)");
     }
     return 0;
+}
+
+extern "C" int vx_augment_batch(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream) {
+    return vx_augment_batch_impl<false>("vx_augment_batch", records, n_image, n_label, x_out, y_out, label_bytes, B, M, D, H, W, stream);
+}
+// the same pass with ops 4..6: chosen by the host only for a table that holds one (the statistics they read were left in the table by vx_augment_stats)
+extern "C" int vx_augment_batch_ext(const void* records, int n_image, int n_label, float* x_out, void* y_out, int label_bytes, int B, int M, int D, int H, int W, void* stream) {
+    return vx_augment_batch_impl<true>("vx_augment_batch_ext", records, n_image, n_label, x_out, y_out, label_bytes, B, M, D, H, W, stream);
 }

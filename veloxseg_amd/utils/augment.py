@@ -5,7 +5,9 @@ random draws are taken on the host from numpy's RandomState in MONAI's order.  T
 Beyond the reference's three: RandFlipd, RandScaleIntensityd, RandShiftIntensityd, RandGaussianNoised and BatchAssembler, which applies them while ONE kernel call
 (csrc/augment_batch.hip) writes the (B, M, D, H, W) batch and its int64 labels; from_config reads train_config["augment"].
 RandAffined / affine_sample / affine_matrix: rotation about all three axes, scale and translation of every sample, key and channel in ONE kernel call
-(csrc/augment_affine.hip); spatial_from_config reads train_config["spatial_augment"]."""
+(csrc/augment_affine.hip); spatial_from_config reads train_config["spatial_augment"].
+RandGaussianSmoothd / RandScaleIntensityFixedMeand / RandAdjustContrastd / blur_separable: a separable blur and the transforms that need a channel's min / max /
+mean / std, whose statistics are reduced on the device and read there by the step program (csrc/augment_blur.hip, csrc/augment_stats.hip)."""
 import math
 
 import numpy as np
@@ -218,9 +220,16 @@ class RandRotated(_Randomizable):
 AUG_RECORD_BYTES, AUG_MAX_STEPS, AUG_LABEL = 192, 8, -1
 AUG_NOISE_STREAM = 0x564158475541          # VX_AUG_NOISE_STREAM of include/veloxseg_hip.h: dropout site ids count up from 1 and never get there
 _OP_MUL, _OP_ADD, _OP_NOISE = 1, 2, 3
+_OP_CONTRAST, _OP_GAMMA, _OP_RETAIN = 4, 5, 6          # read a slot of the device statistics table; known to vx_augment_batch_ext only
+AUG_STAT_BYTES, AUG_STAT_JOB_BYTES, AUG_STAT_PARTIAL_BYTES, AUG_STAT_CHUNK = 32, 16, 24, 4096
+BLUR_RECORD_BYTES, BLUR_MAX_TAIL, BLUR_MAX_SIGMA = 272, 16, 4.0
 _REC = np.dtype([("src", "<u8"), ("stride", "<i8", (3,)), ("dtype", "<i4"), ("b", "<i4"), ("c", "<i4"), ("flip", "<i4"), ("n_steps", "<i4"), ("pad", "<i4", (3,)),
                  ("step", [("op", "<u4"), ("a", "<f4"), ("b", "<f4"), ("key", "<u4")], (AUG_MAX_STEPS,))])
 assert _REC.itemsize == AUG_RECORD_BYTES
+_STAT = np.dtype([("min", "<f4"), ("max", "<f4"), ("mean", "<f4"), ("std", "<f4"), ("s1", "<f8"), ("s2", "<f8")])
+_JOB = np.dtype([("rec", "<i4"), ("upto", "<i4"), ("slot", "<i4"), ("frame", "<i4")])
+_BLUR = np.dtype([("src", "<u8"), ("dst", "<u8"), ("stride", "<i8", (3,)), ("tail", "<i4", (3,)), ("pad", "<i4"), ("w", "<f4", (3, BLUR_MAX_TAIL + 1)), ("pad2", "<i4", (3,))])
+assert (_STAT.itemsize, _JOB.itemsize, _BLUR.itemsize) == (AUG_STAT_BYTES, AUG_STAT_JOB_BYTES, BLUR_RECORD_BYTES)
 
 
 def _flip_mask(spatial_axis):
@@ -263,6 +272,9 @@ def _prob(p):
 class _Program:
     """what the transforms drawn so far do to one key of one sample: a flip mask and the pointwise steps [op, a, b, key, mask of the flips that follow, noise channel]"""
 
+    staged = False           # True once the program needs more than the one pass of vx_augment_batch: a blur, or a step that reads statistics (ops 4..6)
+    blur = None              # or (number of steps in front of the blur, (wD, wH, wW) half weights, the flip mask at the time the blur was added)
+
     def __init__(self):
         self.flip, self.steps = 0, []
 
@@ -271,10 +283,21 @@ class _Program:
         for s in self.steps:
             s[4] ^= mask
 
+    def add_blur(self, halves):
+        if self.blur is not None:
+            raise ValueError("more than one blur fired on one key: a record is materialised once")
+        self.blur, self.staged = (len(self.steps), halves, self.flip), True
+
+    def blur_post(self):
+        """mask of the flips that follow the blur"""
+        return self.flip ^ self.blur[2]
+
     def add_step(self, op, a=0.0, b=0.0, key=0, chan=0):
         if len(self.steps) == AUG_MAX_STEPS:
             raise ValueError(f"more than {AUG_MAX_STEPS} pointwise steps fired on one key: the record holds no more")
         self.steps.append([op, a, b, key, 0, chan])
+        if op >= _OP_CONTRAST:
+            self.staged = True
 
 
 def _check_source(t, what, image):
@@ -306,10 +329,177 @@ def _launch(entries, x_out, y_out, B, M, spatial):
            8, B, M, *spatial, H.stream_ptr())
 
 
+# ---- staged launch: programs with a blur or with statistics steps ------------------------------------------------------------------------
+class _Stage:
+    """host-side plan of one staged call, made without touching the GPU.  records: the final records (images, then labels) followed by one `pre` record per blurred
+    channel (the steps in front of the blur, written to a scratch channel); every record is [source or None (= the blurred scratch channel), code, b, c, flip, steps].
+    rounds_pre / rounds_post: lists of job lists [(record index, upto, slot, frame)], one vx_augment_stats call each, before and after the blur.
+    calls: the names of the C entries in the order they are made."""
+
+
+def _plan(entries):
+    """entries as in _pack, images first -> _Stage.  Round j of a phase resolves the j-th pending statistic of every record that still has one, so the number of
+    vx_augment_stats calls is the depth of the deepest chain that fired and never grows with the number of records."""
+    st = _Stage()
+    n = len(entries)
+    final, pre, st.blurs, pending_pre, pending_post, slots = [], [], [], [], [], 0
+    for i, (t, code, b, c, prog) in enumerate(entries):
+        steps = [list(s) for s in prog.steps]
+        if prog.blur is None:
+            final.append([t, code, b, c, prog.flip, steps])
+            parts = [(i, steps, False)]
+        else:
+            if code != 0:
+                raise ValueError("a blur on a label record")
+            p, halves, post = prog.blur[0], prog.blur[1], prog.blur_post()
+            head = [list(s) for s in steps[:p]]
+            for s in head:
+                s[4] ^= post                                   # the scratch channel is in the blur's frame: flips that follow the blur no longer follow these steps
+            k = len(pre)
+            pre.append([t, 0, k, 0, prog.flip ^ post, head])
+            st.blurs.append((k, halves))
+            final.append([None, 0, b, c, post, steps[p:], k])
+            parts = [(n + k, head, True), (i, steps[p:], False)]
+        for ri, ss, is_pre in parts:
+            jobs, gamma_slot = [], None
+            for k, s in enumerate(ss):
+                if s[0] in (_OP_CONTRAST, _OP_GAMMA, _OP_RETAIN):
+                    jobs.append((ri, k, slots, s[4]))
+                    s[3] = slots
+                    if s[0] == _OP_GAMMA:
+                        gamma_slot = slots
+                    if s[0] == _OP_RETAIN:
+                        if gamma_slot is None:
+                            raise ValueError("a retain-statistics step without the gamma step in front of it")
+                        s[5] = gamma_slot
+                    slots += 1
+            if jobs:
+                # a blurred record: its post-blur statistics wait for the blur; every other record starts in the first round
+                (pending_post if (prog.blur is not None and not is_pre) else pending_pre).append((jobs, is_pre))
+    st.records, st.n_final, st.n_slots = final + pre, n, slots
+    st.n_image = sum(1 for e in entries if e[3] != AUG_LABEL)
+    st.rounds_pre, st.rounds_post = [], []
+    if st.blurs:
+        depth = max([len(j) for j, is_pre in pending_pre if is_pre] or [0])
+        st.rounds_pre = [[j[r] for j, _ in pending_pre if len(j) > r] for r in range(depth)]
+        rest = [j[depth:] for j, is_pre in pending_pre if len(j) > depth] + [j for j, _ in pending_post]
+    else:
+        rest = [j for j, _ in pending_pre]
+    st.rounds_post = [[j[r] for j in rest if len(j) > r] for r in range(max([len(j) for j in rest] or [0]))]
+    ext = lambda recs: any(s[0] >= _OP_CONTRAST for r in recs for s in r[5])
+    st.pre_entry = "vx_augment_batch_ext" if ext(pre) else "vx_augment_batch"
+    st.final_entry = "vx_augment_batch_ext" if ext(final) else "vx_augment_batch"
+    st.calls = (["vx_augment_stats"] * len(st.rounds_pre) + ([st.pre_entry, "vx_blur_batch"] if st.blurs else []) + ["vx_augment_stats"] * len(st.rounds_post)
+                + [st.final_entry])
+    return st
+
+
+def _launch_staged(entries, x_out, y_out, B, M, spatial):
+    """the staged form of _launch: ONE table (records, blur records, job lists and the statistics slots), ONE upload, then the calls of _plan in order; no device -> host
+    copy and no host wait.  Statistics stay on the device."""
+    st = _plan(entries)
+    D, Hh, W = spatial
+    V = D * Hh * W
+    dev = (x_out if x_out is not None else y_out).device
+    nb, nrec = len(st.blurs), len(st.records)
+    rounds = st.rounds_pre + st.rounds_post
+    njobs = sum(len(r) for r in rounds)
+    off_blur = nrec * AUG_RECORD_BYTES
+    off_jobs = off_blur + nb * BLUR_RECORD_BYTES
+    off_stat = off_jobs + njobs * AUG_STAT_JOB_BYTES
+    total = off_stat + st.n_slots * AUG_STAT_BYTES
+    table = torch.empty(total, dtype=torch.uint8, device=dev)                       # allocated first: the records carry addresses inside it
+    base = table.data_ptr()
+    scratch = torch.empty((3, max(nb, 1), V), dtype=torch.float32, device=dev) if nb else None        # materialised, blurred, the blur's tmp
+    host = np.zeros(total, dtype=np.uint8)
+    recs = host[:off_blur].view(_REC)
+    for r, rec in zip(recs, st.records):
+        t, code, b, c, flip, steps = rec[:6]
+        if t is None:
+            r["src"], r["stride"] = scratch[1, rec[6]].data_ptr(), (Hh * W, W, 1)
+        else:
+            r["src"], r["stride"] = t.data_ptr(), t.stride()
+        r["dtype"], r["b"], r["c"], r["flip"], r["n_steps"] = code, b, c, flip, len(steps)
+        if any(s[0] >= _OP_CONTRAST for s in steps):
+            r["pad"][1], r["pad"][2] = np.array([base + off_stat], dtype="<u8").view("<i4")
+        for k, (op, a, sb, key, post, chan) in enumerate(steps):
+            r["step"][k] = (op | (post << 4) | (chan << 8), a, sb, key)
+    blur = host[off_blur:off_jobs].view(_BLUR)
+    for r, (k, halves) in zip(blur, st.blurs):
+        r["src"], r["dst"], r["stride"] = scratch[0, k].data_ptr(), scratch[1, k].data_ptr(), (Hh * W, W, 1)
+        for a in range(3):
+            r["tail"][a] = len(halves[a]) - 1
+            r["w"][a, :len(halves[a])] = halves[a]
+    jobs = host[off_jobs:off_stat].view(_JOB)
+    jobs[:] = [j for r in rounds for j in r] or np.zeros(0, dtype=_JOB)
+    table.copy_(torch.from_numpy(host), non_blocking=False)
+    nchunk = (V + AUG_STAT_CHUNK - 1) // AUG_STAT_CHUNK
+    widest = max([len(r) for r in rounds] or [0])
+    partials = torch.empty(max(widest * nchunk * AUG_STAT_PARTIAL_BYTES, 8), dtype=torch.uint8, device=dev) if rounds else None
+    stream = H.stream_ptr()
+    job_at = [off_jobs]
+
+    def stats(r):
+        H.call("vx_augment_stats", base, nrec, base + job_at[0], len(r), partials.data_ptr(), partials.numel(), D, Hh, W, stream)
+        job_at[0] += len(r) * AUG_STAT_JOB_BYTES
+    for r in st.rounds_pre:
+        stats(r)
+    if nb:
+        H.call(st.pre_entry, base + st.n_final * AUG_RECORD_BYTES, nb, 0, scratch[0].data_ptr(), None, 8, nb, 1, D, Hh, W, stream)
+        H.call("vx_blur_batch", base + off_blur, nb, scratch[2].data_ptr(), D, Hh, W, stream)
+    for r in st.rounds_post:
+        stats(r)
+    H.call(st.final_entry, base, st.n_image, st.n_final - st.n_image, None if x_out is None else x_out.data_ptr(), None if y_out is None else y_out.data_ptr(),
+           8, B, M, D, Hh, W, stream)
+
+
+def program_statistics(entries):
+    """entries: [(float32 (D, H, W) CUDA view, _Program without a blur or a statistics step)], all of one shape -> a DEVICE uint8 tensor of len(entries) slots of
+    AUG_STAT_BYTES bytes (_STAT: min, max, mean, std, S1, S2): the statistics of what each program gives, in the frame of the program's output, in ONE call of
+    vx_augment_stats.  The low-level entry under the statistics transforms; nothing comes back to the host unless the caller copies it."""
+    entries = list(entries)
+    if not entries:
+        raise ValueError("program_statistics: no entries")
+    for i, (t, prog) in enumerate(entries):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"program_statistics: entry {i}: the HIP path needs a CUDA (ROCm) tensor; there is no CPU fallback")
+        if t.dim() != 3 or 0 in t.shape or tuple(t.shape) != tuple(entries[0][0].shape):
+            raise ValueError(f"program_statistics: entry {i}: expected a non-empty (D, H, W) view of the call's shape, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"program_statistics: entry {i}: dtype {t.dtype} not supported (float32)")
+        if prog.staged:
+            raise ValueError(f"program_statistics: entry {i}: the program holds a blur or a statistics step")
+    D, Hh, W = entries[0][0].shape
+    n, dev = len(entries), entries[0][0].device
+    off_jobs = n * AUG_RECORD_BYTES
+    off_stat = off_jobs + n * AUG_STAT_JOB_BYTES
+    table = torch.empty(off_stat + n * AUG_STAT_BYTES, dtype=torch.uint8, device=dev)
+    host = np.zeros(table.numel(), dtype=np.uint8)
+    recs = host[:off_jobs].view(_REC)
+    recs[:] = _pack([(t, 0, 0, 0, prog) for t, prog in entries]).numpy().view(_REC)
+    for r in recs:
+        r["pad"][1], r["pad"][2] = np.array([table.data_ptr() + off_stat], dtype="<u8").view("<i4")
+    host[off_jobs:off_stat].view(_JOB)[:] = [(i, len(prog.steps), i, 0) for i, (_, prog) in enumerate(entries)]
+    table.copy_(torch.from_numpy(host))
+    nchunk = (D * Hh * W + AUG_STAT_CHUNK - 1) // AUG_STAT_CHUNK
+    partials = torch.empty(n * nchunk * AUG_STAT_PARTIAL_BYTES, dtype=torch.uint8, device=dev)
+    H.call("vx_augment_stats", table.data_ptr(), n, table.data_ptr() + off_jobs, n, partials.data_ptr(), partials.numel(), D, Hh, W, H.stream_ptr())
+    return table[off_stat:]
+
+
+def _run(entries, x_out, y_out, B, M, spatial):
+    """today's one call when no program needs more; the staged form otherwise"""
+    if any(e[4].staged for e in entries):
+        _launch_staged(entries, x_out, y_out, B, M, spatial)
+    else:
+        _launch(entries, x_out, y_out, B, M, spatial)
+
+
 class _BatchTransform(_Randomizable):
     """common part of the four dictionary transforms below.  Draw order (modelled on MONAI 1.x, unpinned against MONAI itself, which is not installed): one RandomState
     per transform; every call draws R.rand() < prob FIRST and its parameters ONLY IF that fires; the one draw set of a call is shared by all keys of that call."""
     intensity = True
+    prepares = False          # True: fold takes prepare(draw), not the draw itself
 
     def draw(self):
         """-> None (the call does not fire) or the parameters of this call"""
@@ -318,6 +508,10 @@ class _BatchTransform(_Randomizable):
     def fold(self, params, key_index, chan0, prog):
         """add what this call does to channel `chan0 + (channel within the key)` of key number `key_index` to `prog`"""
         raise NotImplementedError
+
+    def prepare(self, params):
+        """what fold takes for the parameters of one draw (made once per draw, before any GPU work); the draw itself by default"""
+        return params
 
     def __call__(self, data):
         if isinstance(data, list):
@@ -338,6 +532,7 @@ class _BatchTransform(_Randomizable):
         spatial = spatial.pop()
         if 0 in spatial:
             raise ValueError(f"{type(self).__name__}: empty spatial shape {spatial}")
+        params = self.prepare(params)
         entries = []
         M = max([t.shape[0] for _, _, _, t, _ in images] or [1])           # every float32 key is one "sample" of the image output: the channels of a key stay together
         if M > 64:
@@ -359,7 +554,7 @@ class _BatchTransform(_Randomizable):
                 entries.append((t[ch], code, b + ch, AUG_LABEL, prog))
             out[k] = y_out[b:b + t.shape[0], 0]
             b += t.shape[0]
-        _launch(entries, x_out, y_out, max(len(images), nlab, 1), M, spatial)
+        _run(entries, x_out, y_out, max(len(images), nlab, 1), M, spatial)
         return out
 
 
@@ -441,11 +636,210 @@ class RandGaussianNoised(_BatchTransform):
         prog.add_step(_OP_NOISE, float(np.float32(self.mean)), params[0], params[1], chan)
 
 
+# ---- blur, gamma and fixed-mean contrast (csrc/augment_blur.hip, csrc/augment_stats.hip) ---------------------------------------------------
+# Modelled on MONAI 1.x (GaussianFilter(approx="erf") with zero padding, AdjustContrast, ScaleIntensityFixedMean) and UNPINNED against MONAI itself, like the transforms
+# above; tests/augment_stats_ref.py restates the weights, the statistics, the three maps and the draw orders.
+def gaussian_weights(sigma):
+    """fp32 half vector w_0 .. w_tail of MONAI's gaussian_1d(sigma, truncated=4, approx="erf"): tail = int(max(4 sigma, 0.5) + 0.5),
+    w_k = (erf((k + 1/2) / (sigma sqrt 2)) - erf((k - 1/2) / (sigma sqrt 2))) / 2, formed in fp64 and rounded once; not normalised.  0 < sigma <= 4 (tail <= 16)."""
+    sigma = float(sigma)
+    if not (math.isfinite(sigma) and 0.0 < sigma <= BLUR_MAX_SIGMA):
+        raise ValueError(f"sigma {sigma!r} outside (0, {BLUR_MAX_SIGMA}]: the weight table holds a tail of at most {BLUR_MAX_TAIL}")
+    tail = int(max(4.0 * sigma, 0.5) + 0.5)
+    t = 1.0 / (sigma * math.sqrt(2.0))
+    return np.array([0.5 * (math.erf((k + 0.5) * t) - math.erf((k - 0.5) * t)) for k in range(tail + 1)], dtype=np.float64).astype(np.float32)
+
+
+def _half(w, what):
+    """a full odd-length symmetric weight vector -> its fp32 half w_0 .. w_tail (the centre first)"""
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if w.size % 2 != 1:
+        raise ValueError(f"{what}: {w.size} weights: the length must be odd")
+    tail = w.size // 2
+    if tail > BLUR_MAX_TAIL:
+        raise ValueError(f"{what}: a tail of {tail} (at most {BLUR_MAX_TAIL})")
+    w32 = w.astype(np.float32)
+    if not np.isfinite(w32).all():
+        raise ValueError(f"{what}: weights must be finite")
+    if not np.array_equal(w32, w32[::-1]):
+        raise ValueError(f"{what}: the weights are not symmetric")
+    return w32[tail:].copy()
+
+
+def blur_separable(entries, out=None):
+    """entries: [(source (D, H, W) float32 CUDA view, (wD, wH, wW))], every w an odd-length symmetric weight vector of at most 2 * 16 + 1 taps, all sources of ONE shape
+    -> one contiguous (D, H, W) float32 tensor per entry, in ONE call of vx_blur_batch (three launches whatever the number of entries; the rule:
+    include/veloxseg_hip.h): passes W, H, D, zeros outside the patch, y = w_0 x_0 + sum_k w_k (x_-k + x_+k) with the pair added first.  Sources may be any strided
+    views (no .contiguous()).  `out`: the destinations (contiguous float32, not overlapping a source), else they are allocated.  Everything is checked before any GPU
+    work; there is no CPU fallback."""
+    entries = [tuple(e) for e in entries]
+    if not entries:
+        raise ValueError("blur_separable: no entries")
+    shape, halves = None, []
+    for i, e in enumerate(entries):
+        if len(e) != 2:
+            raise ValueError(f"blur_separable: entry {i} has {len(e)} fields (source, (wD, wH, wW))")
+        src, ws = e
+        if not (isinstance(src, torch.Tensor) and src.is_cuda):
+            raise RuntimeError(f"blur_separable: entry {i}: the HIP path needs a CUDA (ROCm) tensor; there is no CPU fallback")
+        if src.dim() != 3 or 0 in src.shape:
+            raise ValueError(f"blur_separable: entry {i}: expected a non-empty (D, H, W) view, got {tuple(src.shape)}")
+        if src.dtype != torch.float32:
+            raise TypeError(f"blur_separable: entry {i}: dtype {src.dtype} not supported (float32)")
+        shape = tuple(src.shape) if shape is None else shape
+        if tuple(src.shape) != shape:
+            raise ValueError(f"blur_separable: entry {i} has the shape {tuple(src.shape)}, the call {shape}")
+        ws = list(ws)
+        if len(ws) != 3:
+            raise ValueError(f"blur_separable: entry {i}: three weight vectors (D, H, W), got {len(ws)}")
+        halves.append([_half(w, f"blur_separable: entry {i} axis {a}") for a, w in enumerate(ws)])
+    dev = entries[0][0].device
+    if out is None:
+        out = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in entries]
+    out = list(out)
+    if len(out) != len(entries) or any(not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == shape) for o in out):
+        raise ValueError(f"blur_separable: `out` must hold one contiguous float32 {shape} CUDA tensor per entry")
+    for i, (src, _) in enumerate(entries):
+        lo = src.data_ptr()
+        hi = lo + (sum((n - 1) * abs(s) for n, s in zip(src.shape, src.stride())) + 1) * 4
+        for j, o in enumerate(out):
+            if o.data_ptr() < hi and lo < o.data_ptr() + o.numel() * 4:
+                raise ValueError(f"blur_separable: the destination of entry {j} overlaps the source of entry {i}")
+    tab = np.zeros(len(entries), dtype=_BLUR)
+    for r, (src, _), o, hv in zip(tab, entries, out, halves):
+        r["src"], r["dst"], r["stride"] = src.data_ptr(), o.data_ptr(), src.stride()
+        for a in range(3):
+            r["tail"][a] = len(hv[a]) - 1
+            r["w"][a, :len(hv[a])] = hv[a]
+    table = torch.from_numpy(tab.view(np.uint8).reshape(-1)).to(dev)
+    tmp = torch.empty((len(entries),) + shape, dtype=torch.float32, device=dev)
+    H.call("vx_blur_batch", table.data_ptr(), len(entries), tmp.data_ptr(), *shape, H.stream_ptr())
+    return out
+
+
+def _sigma_range(v, what):
+    if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool):
+        lo = hi = float(v)
+    else:
+        try:
+            pair = [float(t) for t in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} {v!r}: a number or a pair of numbers") from None
+        if len(pair) != 2:
+            raise ValueError(f"{what} {v!r}: a number or a pair of numbers")
+        lo, hi = (min(pair), max(pair)) if all(math.isfinite(t) for t in pair) else (float("nan"),) * 2
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo and hi <= BLUR_MAX_SIGMA):
+        raise ValueError(f"{what} {v!r} outside (0, {BLUR_MAX_SIGMA}]: the weight table holds a tail of at most {BLUR_MAX_TAIL}")
+    return lo, hi
+
+
+class RandGaussianSmoothd(_BatchTransform):
+    """MONAI RandGaussianSmoothd(keys, sigma_x, sigma_y, sigma_z, approx, prob): a separable Gaussian blur with zero padding; sigma_x is the FIRST spatial axis (D), as
+    in MONAI.  Weights: gaussian_weights (erf, truncated at 4 sigma, not normalised); sigma <= 4 and approx = "erf" only.
+    Draw order (MONAI 1.x, unpinned): R.rand() < prob, then, only if it fires, sigma_x, sigma_y, sigma_z = R.uniform(low, high) each; one set for all keys."""
+
+    prepares = True
+
+    def __init__(self, keys, sigma_x=(0.25, 1.5), sigma_y=(0.25, 1.5), sigma_z=(0.25, 1.5), approx="erf", prob=0.1):
+        if approx != "erf":
+            raise NotImplementedError(f"RandGaussianSmoothd: approx {approx!r} is not implemented on the HIP path (erf)")
+        self.keys, self.prob = list(keys), _prob(prob)
+        self.sigma = [_sigma_range(v, f"sigma_{n}") for v, n in zip((sigma_x, sigma_y, sigma_z), "xyz")]
+        self.set_random_state()
+
+    def draw(self):
+        if not self.R.rand() < self.prob:
+            return None
+        return tuple(float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.sigma)
+
+    def fold(self, params, key_index, chan, prog):
+        if not isinstance(params, _Weights):
+            raise TypeError("RandGaussianSmoothd.fold takes the weights of its draw")
+        prog.add_blur(params.halves)
+
+    def prepare(self, params):
+        return _Weights([gaussian_weights(s) for s in params])
+
+
+class _Weights:
+    """the three half weight vectors of one blur draw, made once per draw and shared by the keys and channels it is folded into"""
+
+    def __init__(self, halves):
+        self.halves = halves
+
+
+class RandScaleIntensityFixedMeand(_BatchTransform):
+    """MONAI RandScaleIntensityFixedMeand(keys, factors, fixed_mean=True, preserve_range, prob): ((v - mean) * fp32(1 + f)) + mean, then a clamp to the channel's [min, max]
+    when preserve_range; every operation rounded to fp32 on its own.  mean / min / max: of the CHANNEL as it enters the step, reduced on the device.
+    Draw order (MONAI 1.x, unpinned): R.rand() < prob, then, only if it fires, f = R.uniform(-factors, factors) (a pair gives low, high); one f for all keys."""
+
+    def __init__(self, keys, factors=0, fixed_mean=True, preserve_range=False, prob=0.1, channel_wise=False):
+        if not fixed_mean:
+            raise NotImplementedError("RandScaleIntensityFixedMeand: fixed_mean=False is RandScaleIntensityd")
+        if channel_wise:
+            raise NotImplementedError("RandScaleIntensityFixedMeand: channel_wise=True (one factor per channel) is not implemented on the HIP path")
+        self.keys, self.prob, self.factors, self.preserve_range = list(keys), _prob(prob), _range(factors, "factors"), bool(preserve_range)
+        self.set_random_state()
+
+    def draw(self):
+        if not self.R.rand() < self.prob:
+            return None
+        return float(np.float32(1.0 + self.R.uniform(low=self.factors[0], high=self.factors[1])))
+
+    def fold(self, params, key_index, chan, prog):
+        prog.add_step(_OP_CONTRAST, params, 1.0 if self.preserve_range else 0.0)
+
+
+class RandAdjustContrastd(_BatchTransform):
+    """MONAI RandAdjustContrastd(keys, prob, gamma, invert_image, retain_stats): v' = powf((v - min) / (r + 1e-7f), g) * r + min with r = max - min; invert_image negates the
+    channel before the statistics are taken and negates the result; retain_stats then writes (v' - mean2) / (std2 + 1e-8f) * std1 + mean1 (mean1, std1 of the input, mean2,
+    std2 of v').  A number g for `gamma` means (0.5, g).  The statistics are PER CHANNEL: MONAI's value for a one-channel key; for a multi-channel key MONAI's AdjustContrast
+    takes min / max over the whole tensor -- a deviation.
+    Draw order (MONAI 1.x, unpinned): R.rand() < prob, then, only if it fires, g = R.uniform(low, high); one g for all keys."""
+
+    def __init__(self, keys, prob=0.1, gamma=(0.5, 4.5), invert_image=False, retain_stats=False):
+        if isinstance(gamma, (int, float, np.integer, np.floating)) and not isinstance(gamma, bool):
+            if gamma <= 0.5:
+                raise ValueError(f"if gamma is a number, it must be greater than 0.5 and is taken as the range (0.5, gamma); got {gamma!r}")
+            lo, hi = 0.5, float(gamma)
+        else:
+            try:
+                pair = [float(t) for t in gamma]
+            except (TypeError, ValueError):
+                raise ValueError(f"gamma {gamma!r}: a number or a pair of numbers") from None
+            if len(pair) != 2:
+                raise ValueError(f"gamma should be a number or pair of numbers, got {gamma!r}")
+            lo, hi = (min(pair), max(pair)) if all(math.isfinite(t) for t in pair) else (float("nan"),) * 2
+        if not (math.isfinite(lo) and math.isfinite(hi)) or lo < 0:
+            raise ValueError(f"gamma {gamma!r}: finite and non-negative")
+        self.keys, self.prob, self.gamma, self.invert_image, self.retain_stats = list(keys), _prob(prob), (lo, hi), bool(invert_image), bool(retain_stats)
+        self.set_random_state()
+
+    def draw(self):
+        if not self.R.rand() < self.prob:
+            return None
+        return float(np.float32(self.R.uniform(low=self.gamma[0], high=self.gamma[1])))
+
+    def fold(self, params, key_index, chan, prog):
+        if len(prog.steps) + 1 + 2 * self.invert_image + self.retain_stats > AUG_MAX_STEPS:
+            raise ValueError(f"more than {AUG_MAX_STEPS} pointwise steps fired on one key: the record holds no more")
+        if self.invert_image:
+            prog.add_step(_OP_MUL, -1.0)
+        prog.add_step(_OP_GAMMA, params)
+        if self.retain_stats:
+            prog.add_step(_OP_RETAIN)
+        if self.invert_image:
+            prog.add_step(_OP_MUL, -1.0)
+
+
 class BatchAssembler:
-    """the four transforms above, in any order, applied while the batch is assembled: samples (a list of dicts of (C, D, H, W) CUDA tensors, the output of the crop /
+    """the transforms above, in any order (at most one RandGaussianSmoothd), applied while the batch is assembled: samples (a list of dicts of (C, D, H, W) CUDA tensors, the output of the crop /
     rotation chain) -> (x (B, M, D, H, W) float32, y (B, 1, D, H, W) int64) with the bytes of running `transforms` as a Compose on each sample in turn and then
     torch.cat over image_keys, .long() of the label and torch.stack -- in ONE call of vx_augment_batch (one table, one upload, at most two launches).
-    Draws: sample by sample, transform by transform, exactly what that Compose would draw.  Sources may be views (no .contiguous())."""
+    Draws: sample by sample, transform by transform, exactly what that Compose would draw.  Sources may be views (no .contiguous()).
+    When a blur or a statistics transform FIRES in a batch, the call is staged (_plan / _launch_staged): still one table and one upload, one
+    vx_augment_stats call per round of pending statistics, one materialise + vx_blur_batch pair, then the final pass; the launch count follows the deepest chain that
+    fired, never B or M, and nothing comes back to the host.  When none fires, the calls and the table bytes are those of the one-pass form."""
 
     def __init__(self, image_keys, label_key, transforms):
         self.image_keys, self.label_key, self.transforms = list(image_keys), label_key, list(transforms)
@@ -454,11 +848,14 @@ class BatchAssembler:
         known = set(self.image_keys) | {label_key}
         for t in self.transforms:
             if not isinstance(t, _BatchTransform):
-                raise TypeError(f"BatchAssembler: {type(t).__name__} is not one of RandFlipd, RandScaleIntensityd, RandShiftIntensityd, RandGaussianNoised")
+                raise TypeError(f"BatchAssembler: {type(t).__name__} is not one of RandFlipd, RandScaleIntensityd, RandShiftIntensityd, RandGaussianNoised, "
+                                "RandGaussianSmoothd, RandScaleIntensityFixedMeand, RandAdjustContrastd")
             if set(t.keys) - known:
                 raise ValueError(f"BatchAssembler: {type(t).__name__} names keys {sorted(set(t.keys) - known)} that the batch does not hold")
             if t.intensity and label_key in t.keys:
                 raise ValueError(f"BatchAssembler: {type(t).__name__} on the label key {label_key!r}")
+        if sum(isinstance(t, RandGaussianSmoothd) for t in self.transforms) > 1:
+            raise ValueError("BatchAssembler: more than one RandGaussianSmoothd in the transform list: a record is materialised for a blur once")
 
     def set_random_state(self, seed=None):
         rs = np.random.RandomState(seed)
@@ -497,6 +894,8 @@ class BatchAssembler:
                 params = t.draw()
                 if params is None:
                     continue
+                if t.prepares:
+                    params = t.prepare(params)
                 chan0 = 0
                 for ki, k in enumerate(t.keys):
                     for ch, prog in enumerate(progs[k]):
@@ -511,17 +910,21 @@ class BatchAssembler:
         B = len(samples)
         x = torch.empty((B, M) + spatial, dtype=torch.float32, device=device)
         y = torch.empty((B, 1) + spatial, dtype=torch.int64, device=device)
-        _launch(images + labels, x, y, B, M, spatial)
+        _run(images + labels, x, y, B, M, spatial)
         return x, y
 
 
-_CONFIG_KEYS = ("flip_axes", "flip_prob", "scale", "scale_prob", "shift", "shift_prob", "noise_std", "noise_prob")
+_CONFIG_KEYS = ("flip_axes", "flip_prob", "scale", "scale_prob", "shift", "shift_prob", "noise_std", "noise_prob", "blur_sigma", "blur_prob", "contrast_factors",
+                "contrast_prob", "contrast_preserve_range", "gamma_range", "gamma_prob", "gamma_invert", "gamma_retain_stats")
 
 
 def from_config(cfg, image_keys, label_key):
     """train_config["augment"] -> BatchAssembler.  Keys (all optional; an unknown key raises ValueError): flip_axes (list of 0 = D, 1 = H, 2 = W: one RandFlipd per
     axis, each with flip_prob, default 0.5, on images and label), scale / scale_prob (RandScaleIntensityd factors, default prob 0.1), shift / shift_prob
-    (RandShiftIntensityd offsets, 0.1), noise_std / noise_prob (RandGaussianNoised std with sample_std=True, 0.1); the order is flips, scale, shift, noise."""
+    (RandShiftIntensityd offsets, 0.1), noise_std / noise_prob (RandGaussianNoised std with sample_std=True, 0.1), blur_sigma / blur_prob (RandGaussianSmoothd: a number
+    or a (low, high) pair for all three axes, default prob 0.2), contrast_factors / contrast_prob / contrast_preserve_range (RandScaleIntensityFixedMeand, 0.15, False),
+    gamma_range / gamma_prob / gamma_invert / gamma_retain_stats (RandAdjustContrastd, 0.1; gamma_invert: true puts an inverted RandAdjustContrastd in front of the plain
+    one, each with gamma_prob); the order is flips, scale, shift, noise, blur, contrast, gamma."""
     if not isinstance(cfg, dict):
         raise ValueError(f"augment config must be a dict, got {type(cfg).__name__}")
     unknown = sorted(set(cfg) - set(_CONFIG_KEYS))
@@ -539,6 +942,17 @@ def from_config(cfg, image_keys, label_key):
         ts.append(RandShiftIntensityd(image_keys, offsets=cfg["shift"], prob=cfg.get("shift_prob", 0.1)))
     if cfg.get("noise_std") is not None:
         ts.append(RandGaussianNoised(image_keys, prob=cfg.get("noise_prob", 0.1), mean=0.0, std=cfg["noise_std"]))
+    if cfg.get("blur_sigma") is not None:
+        sg = cfg["blur_sigma"]
+        ts.append(RandGaussianSmoothd(image_keys, sigma_x=sg, sigma_y=sg, sigma_z=sg, prob=cfg.get("blur_prob", 0.2)))
+    if cfg.get("contrast_factors") is not None:
+        ts.append(RandScaleIntensityFixedMeand(image_keys, factors=cfg["contrast_factors"], preserve_range=bool(cfg.get("contrast_preserve_range", False)),
+                                               prob=cfg.get("contrast_prob", 0.15)))
+    if cfg.get("gamma_range") is not None:
+        retain = bool(cfg.get("gamma_retain_stats", False))
+        if cfg.get("gamma_invert", False):
+            ts.append(RandAdjustContrastd(image_keys, prob=cfg.get("gamma_prob", 0.1), gamma=cfg["gamma_range"], invert_image=True, retain_stats=retain))
+        ts.append(RandAdjustContrastd(image_keys, prob=cfg.get("gamma_prob", 0.1), gamma=cfg["gamma_range"], retain_stats=retain))
     return BatchAssembler(image_keys, label_key, ts)
 
 

@@ -53,7 +53,8 @@ class SyntheticVolumes:
     """whole synthetic cases (padded background + a foreground body + lesion blobs) pushed through the reference's transform chain on the GPU
     (utils/augment.py: CropForegroundd -> RandCropByPosNegLabeld(num_samples) -> RandRotated): `batch` patches per step, batch / num_samples cases per step.
     augment: None (the chain above, batches put together with cat / stack / .long()) or the train_config["augment"] dict of utils.augment.from_config: mirror, scale,
-    shift and noise drawn per patch and applied while ONE kernel call writes the batch (utils.augment.BatchAssembler).
+    shift and noise drawn per patch and applied while ONE kernel call writes the batch (utils.augment.BatchAssembler); with the blur_* / contrast_* / gamma_* keys also
+    Gaussian blur, fixed-mean contrast and gamma, whose channel statistics are reduced and read on the device (a batch in which one fires takes a few more launches).
     spatial: None (the chain above) or the train_config["spatial_augment"] dict of utils.augment.spatial_from_config: RandAffined (rotation about all three axes,
     scale, translation; ONE kernel call for all patches of a case) takes the place of the chain's RandRotated; with its `context` on, the crop hands over views
     (copy=False) and the sampler reads the volume around each patch"""
