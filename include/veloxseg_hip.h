@@ -583,6 +583,19 @@ int vx_sw_blend_finalize(const float* acc, float* out, unsigned char* labels, co
                          int C, int D, int H, int W, void* stream);
 /* labels[b, v] = argmax_c logits[b, c, v] (first maximum, uint8): `outputs[0].argmax(dim=1)` of utils/metric/metrics.py:16 */
 int vx_argmax_channels(const float* logits, unsigned char* labels, int B, int C, long V, void* stream);
+/* ---- ensemble inference: mean soft-max probabilities of several models, their labels and entropy (utils/ensemble.py) ----
+ * logits, psum: (B, K, V) fp32 contiguous, 1 <= K <= 256, not aliased.  Both entries check their arguments before they launch (-1), use no atomics and give the same
+ * bits every run.  Four voxels per thread with 16-byte accesses where V % 4 == 0 and the base pointers themselves are 16-byte aligned (labels: 4-byte); one otherwise.
+ *
+ * psum[b, c, v] = (first ? 0 : psum[b, c, v]) + weight * softmax_c(logits[b, :, v]); with first != 0 psum is written and never read (no zeros launch, a NaN in it does
+ * not leak).  Per column: m = max_c x_c, e_c = expf(x_c - m) (the accurate one), s = the e_c added in class order, p_c = e_c / s in IEEE fp32; weight * p_c and the add
+ * are two roundings, never an fma.  As from torch.softmax, a column with a NaN, a column with a +inf and a column of -inf only come out all-NaN; a -inf beside a finite
+ * maximum contributes exactly 0.  Columns of K <= 8 classes are read once and kept in registers, longer ones are read three times; the bits are the same. */
+int vx_softmax_accumulate(const float* logits, float* psum, int B, int K, long V, float weight, int first, void* stream);
+/* labels[b, v] = uint8 arg-max_c psum[b, c, v] by the rule of vx_sw_finalize (first NaN, else first maximum): byte for byte vx_argmax_channels(psum).
+ * entropy[b, v] = sum_c -(p ln p) with logf in fp32, the terms added in class order from +0, every product and sum rounded; p == 0 contributes exactly +0, a one-hot
+ * column gives +0.0 (not -0.0), a column with a NaN gives NaN.  Either output may be NULL, not both. */
+int vx_prob_finalize(const float* psum, unsigned char* labels, float* entropy, int B, int K, long V, void* stream);
 /* conf[b, g, p] += #voxels with ground truth g and prediction p (uint64, NC*NC per sample; caller zeroes it): the sufficient statistic of
  * metrics_tensor (utils/metric/metrics.py:44-91) and cal_dice (utils/metric/metrics_brats.py:31-35); label widths (pred, gt) in bytes: (1,1), (1,4), (1,8), (4,4),
  * (8,1), (8,8), any other pair fails with -3; 2 <= NC <= 8.  A label is clamped in its own width before it is counted: < 0 is class 0, >= NC is class NC-1. */

@@ -142,16 +142,8 @@ __global__ void __launch_bounds__(256) vx_sw_mirror_accumulate_k(const float* __
 // The weight of a window voxel is w[z, y, x] = max((g[z] * g[rd + y]) * g[rd + rh + x], floor): three host-made axis tables behind one pointer and a clamp that makes
 // w non-separable.  It is formed in registers from the tables (a few hundred floats, cache-resident), never stored as a volume; both products are rounded.
 // The weights are not powers of two, so acc + w * p contracted into an fma is NOT the bits of the product followed by the sum.  This toolchain's __fmul_rn / __fadd_rn are
-// the plain operators and are contracted like them (the section-21 kernels above only ever scale by a power of two, where the fma gives the same bits); the operators
-// below are emitted under `fp contract(off)` and stay a v_mul_f32 and a v_add_f32.
-__device__ __forceinline__ float vx_mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float vx_add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
+// the plain operators and are contracted like them (the section-21 kernels above only ever scale by a power of two, where the fma gives the same bits); vx_mul_rn /
+// vx_add_rn (vx_common.h) are emitted under `fp contract(off)` and stay a v_mul_f32 and a v_add_f32.
 __device__ __forceinline__ float vx_blend_w(float gzy, float gx, float floor) { return fmaxf(vx_mul_rn(gzy, gx), floor); }
 
 // acc[c, z0+z, y0+y, x0+x] += w[z, y, x] * p,  p = pred[c, m_z(z), m_y(y), m_x(x)] (MIRROR false: wsum is not read) or weight * (wsum[c, z, y, x] + that) (MIRROR true):

@@ -82,6 +82,19 @@ __device__ __forceinline__ void vx_st1(vx_bf16* p, long i, float v) { p[i].v = (
 template <typename T> __device__ __forceinline__ float vx_round_as(float v) { return v; }
 template <> __device__ __forceinline__ float vx_round_as<vx_bf16>(float v) { return vx_bf16_lo(vx_pack_bf16x2(v, 0.0f)); }
 
+// ---- products and sums that must stay two roundings --------------------------------------------------------------------------------------------------------
+// Where a factor is not a power of two (the Gaussian window weights of csrc/infer.hip, the ensemble weights 1/3, 1/5 of csrc/ensemble.hip), acc + w * p contracted into
+// an fma is NOT the bits of the product followed by the sum.  This toolchain's __fmul_rn / __fadd_rn are the plain operators and are contracted like them; the operators
+// below are emitted under `fp contract(off)` and stay a v_mul_f32 and a v_add_f32.
+__device__ __forceinline__ float vx_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float vx_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 // ---- XCD-aware block coordinates (round 6) --------------------------------------------------------------------------------------------------------
 // The blocks of a 2-D grid are dispatched in linear order (x fastest) and consecutive linear ids go to different XCDs (8 L2 slices).  When the blocks of one ROW (same
 // blockIdx.y: one attention window, one sample ...) share their operands, the row is spread over all eight L2s and every one of them fetches the operands from HBM.
