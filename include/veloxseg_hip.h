@@ -763,6 +763,42 @@ int vx_cc_tally(const int* cc, const void* other, int other_bytes, long V, int N
 /* out[v] = keep[cc[v]] ? in[v] : 0 (keep: N + 1 bytes; an id outside 0..N is dropped); in / out of lab_bytes 1 / 4 / 8; out may be in itself */
 int vx_cc_select(const int* cc, const unsigned char* keep, int N, const void* in, void* out, int lab_bytes, long V, void* stream);
 
+/* ---- mask morphology (csrc/morphology.hip): bit-packed dilation / erosion, inner boundary, hole filling of label maps -------------
+ * No counterpart in the reference.  One sample per call; label maps are uint8 / int32 / int64 (bytes 1 / 4 / 8).  Integer work only: equal inputs give equal
+ * bits.  Every entry checks pointers, extents (each > 0, D * H * W <= 2^31 - 1), widths, connectivity (6 / 18 / 26, the meaning vx_cc_label gives the word, the
+ * centre included: scipy's generate_binary_structure(3, 1 | 2 | 3)), op, mode and iterations before any launch; a refused call returns -1 and writes nothing.
+ *
+ * Packed layout: unsigned long long bits[D * H * Wq], Wq = (W + 63) / 64; rows start on word boundaries, bit i of word q of row (z, y) is voxel x = 64 q + i.
+ * The tail bits of a row's last word are ZERO in every output and IGNORED in every input.  vx_morph_words = D * H * Wq (it fits an int: Wq <= W);
+ * vx_morph_grid_cap() = the block count above which every kernel here loops; vx_morph_max_fused() = the iterations one launch of the step kernel runs: 1 (a
+ * fused LDS form was measured slower than chained launches and is not kept).
+ *
+ * vx_morph_pack: bit = lab != 0 (match 0) or lab == value (match 1), compared as raw values of lab_bytes; one wave ballot per word.
+ * vx_morph_step: op 0 dilates (out[v] = OR of in[v + o] over the offsets), op 1 erodes (AND), `iterations` >= 1 times; voxels outside the volume read
+ * border_value (0 / 1).  An iteration count above D + H + W is cut there (the result is stationary by then).  in is never written; in, out and tmp are three
+ * different buffers of vx_morph_words words; tmp is needed when iterations > vx_morph_max_fused() (NULL otherwise): launches alternate between out and tmp
+ * so that the last one writes out.  vx_morph_boundary: out = in & ~erode(in, connectivity, 1 iteration, border_value 0); out != in.
+ * vx_morph_unpack (out may be in; in may be NULL in mode 0): mode 0 MASK out = bit (0 / 1), 1 KEEP out = bit ? in : 0, 2 RESTRICT out = (in == value && !bit) ? 0
+ * : in, 3 PAINT out = (bit && in == 0) ? value : in. */
+int vx_morph_words(int D, int H, int W);
+int vx_morph_grid_cap(void);
+int vx_morph_max_fused(void);
+int vx_morph_pack(const void* lab, int lab_bytes, long value, int match, unsigned long long* bits, int D, int H, int W, void* stream);
+int vx_morph_step(const unsigned long long* in, unsigned long long* out, unsigned long long* tmp, int D, int H, int W, int op, int connectivity, int iterations,
+                  int border_value, void* stream);
+int vx_morph_boundary(const unsigned long long* in, unsigned long long* out, int D, int H, int W, int connectivity, void* stream);
+int vx_morph_unpack(const unsigned long long* bits, const void* in, void* out, int lab_bytes, long value, int mode, int D, int H, int W, void* stream);
+/* Hole filling (MONAI's FillHoles restated; for a {0, 1} map scipy.ndimage.binary_fill_holes): vx_morph_background writes bg = (lab == 0) as uint8, the input of
+ * vx_cc_label, whose map cc (ids 1..N on the background) the next two read.  vx_hole_scan: the caller sets lo[0..N] = INT64_MAX, hi[0..N] = INT64_MIN, open[0..N]
+ * = 0; for every background voxel, open[id] = 1 if a neighbour lies outside the volume, and the values of its in-volume neighbours with lab != 0 go into lo[id]
+ * (min) and hi[id] (max) as signed 64-bit numbers (a 1-byte label is 0..255).  Only voxels that see a face or a foreground neighbour send anything, one atomic
+ * per run of equal ids in a wave.  vx_hole_fill: out[v] = lab[v] where lab[v] != 0; else lo[id] when !open[id] && lo[id] == hi[id] && (n_applied == 0 || lo[id]
+ * is one of applied[0..n_applied)); else 0.  out may be lab. */
+int vx_morph_background(const void* lab, int lab_bytes, unsigned char* bg, long V, void* stream);
+int vx_hole_scan(const void* lab, int lab_bytes, const int* cc, int N, int D, int H, int W, int connectivity, long long* lo, long long* hi, int* open, void* stream);
+int vx_hole_fill(const void* lab, void* out, int lab_bytes, const int* cc, int N, const long long* lo, const long long* hi, const int* open, const long long* applied,
+                 int n_applied, long V, void* stream);
+
 /* ---- dense strided convolution on MFMA (groups = 1; k odd <= 7, stride 2..4, pad = k / 2): the DownConv layers between the encoder levels and the
  * stem (Encoder.py:29-58, conv_blocks.py:8-27 of the reference).  Implicit GEMM on v_mfma_f32_16x16x4_f32, fp32 in / fp32 accumulate.  ws =
  * vx_conv_mfma_ws_floats(Cin, Cout, K, backward) floats for the operand-order weight image (written by every call).  bwd_data: accumulate = 1 adds

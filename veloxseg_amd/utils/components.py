@@ -10,7 +10,7 @@ import torch
 from .. import _hip as H
 
 _BYTES = {torch.bool: 1, torch.uint8: 1, torch.int32: 4, torch.int64: 8}
-_KEYS = ("min_voxels", "keep_largest", "connectivity", "binary")
+_KEYS = ("min_voxels", "keep_largest", "connectivity", "binary", "closing", "opening", "fill_holes", "morph_connectivity", "labels")
 
 
 def _samples(labels, what):
@@ -128,14 +128,24 @@ def keep_largest_components(labels: torch.Tensor, k: int = 1, connectivity: int 
 
 class Postprocess:
     """Mask clean-up after the arg-max, from test_config["postprocess"]: {"min_voxels": n} drops smaller components, {"keep_largest": k} keeps the k largest (both:
-    the small ones go first), "connectivity" 6 / 18 / 26 (default 26), "binary" joins all non-zero classes before labelling.  No settings: the identity."""
+    the small ones go first), "connectivity" 6 / 18 / 26 (default 26), "binary" joins all non-zero classes before labelling.  Morphology (utils/morphology.py,
+    DESIGN.md section 31) runs ahead of them: {"closing": n} and {"opening": n} are close_labels / open_labels with n iterations, {"fill_holes": true} is fill_holes;
+    "morph_connectivity" 6 / 18 / 26 (default 6) is their structuring element, "labels" the classes they work on (a list, processed in its order; None: the
+    foreground labels != 0 as one mask for closing and opening, every class for fill_holes).  The order is fixed:
+    closing -> fill_holes -> opening -> min_voxels -> keep_largest.  No settings: the identity."""
 
-    def __init__(self, min_voxels=None, keep_largest=None, connectivity=26, binary=False):
+    def __init__(self, min_voxels=None, keep_largest=None, connectivity=26, binary=False, closing=None, opening=None, fill_holes=False, morph_connectivity=6,
+                 labels=None):
         self.min_voxels = None if min_voxels is None else int(min_voxels)
         self.keep_largest = None if keep_largest is None else int(keep_largest)
         if self.min_voxels is not None and self.min_voxels < 0 or self.keep_largest is not None and self.keep_largest < 0:
             raise ValueError("Postprocess: min_voxels and keep_largest must not be negative")
         self.connectivity, self.binary = _connectivity(connectivity), bool(binary)
+        self.closing, self.opening = (int(n) if n else None for n in (closing, opening))          # 0 iterations: unset
+        if any(n is not None and n < 0 for n in (self.closing, self.opening)):
+            raise ValueError("Postprocess: closing and opening iterations must not be negative")
+        self.fill_holes, self.morph_connectivity = bool(fill_holes), _connectivity(morph_connectivity)
+        self.labels = None if labels is None else [int(c) for c in labels]
 
     @classmethod
     def from_config(cls, cfg):
@@ -147,9 +157,17 @@ class Postprocess:
 
     @property
     def identity(self):
-        return self.min_voxels is None and self.keep_largest is None
+        return self.min_voxels is None and self.keep_largest is None and self.closing is None and self.opening is None and not self.fill_holes
 
     def __call__(self, labels: torch.Tensor) -> torch.Tensor:
+        if self.closing is not None or self.opening is not None or self.fill_holes:
+            from . import morphology as M
+            if self.closing is not None:
+                labels = M.close_labels(labels, self.morph_connectivity, self.closing, self.labels)
+            if self.fill_holes:
+                labels = M.fill_holes(labels, self.morph_connectivity, self.labels)
+            if self.opening is not None:
+                labels = M.open_labels(labels, self.morph_connectivity, self.opening, self.labels)
         if self.min_voxels is not None:
             labels = remove_small_components(labels, self.min_voxels, self.connectivity, self.binary)
         if self.keep_largest is not None:
