@@ -39,8 +39,9 @@ __global__ void __launch_bounds__(256) vx_seg_loss_fwd_k(const float* __restrict
             for (int c = 0; c < VX_MAXC; ++c) if (c < C) { if (c == y) zy = z[c]; z[c] = expf(z[c] - mx); se += z[c]; }
             const float inv = 1.0f / se;
             // cross entropy through log-sum-exp, as nn.CrossEntropyLoss computes it: grows linearly with the logit gap instead of saturating at
-            // -log(FLT_MIN) like -log(softmax) does (labels outside [0, C) contribute nothing; the python surface validates the range)
-            if ((unsigned)y < (unsigned)C) ce += (mx + logf(se)) - zy;
+            // -log(FLT_MIN) like -log(softmax) does (labels outside [0, C) contribute nothing; the python surface validates the range).  The gap z_y - mx is
+            // formed FIRST: (mx + log se) - z_y rounds the small logarithm to the ulp of the logits, half of 1e-3 per voxel under a common offset of 1e4.
+            if ((unsigned)y < (unsigned)C) ce += logf(se) - (zy - mx);
 #pragma unroll
             for (int c = 0; c < VX_MAXC; ++c) if (c < C) {
                 const float p = z[c] * inv;
@@ -119,7 +120,7 @@ __global__ void __launch_bounds__(256) vx_seg_loss_fwd4_k(const float* __restric
                     for (int c = 0; c < C; ++c) {
                         const float pc = e[c] * inv;
                         S[h][1 + C + c] += pc;
-                        if (c == y[j]) { S[h][1 + c] += pc; S[h][0] += (mx + logf(se)) - z[c][j]; }     // CE = logsumexp - z_y (nn.CrossEntropyLoss)
+                        if (c == y[j]) { S[h][1 + c] += pc; S[h][0] += logf(se) - (z[c][j] - mx); }     // CE = logsumexp - z_y (nn.CrossEntropyLoss), the gap first (see vx_seg_loss_fwd_k)
                     }
                 }
             }

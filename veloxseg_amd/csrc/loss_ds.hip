@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) vx_seg_loss_ds_fwd_k(VxDs P, const void* 
                     for (int c = 0; c < C; ++c) {
                         const float pc = e[c] * inv;
                         S[h][1 + C + c] += pc;
-                        if (c == y[j]) { S[h][1 + c] += pc; S[h][0] += (mx + __logf(se)) - z[c][j]; }
+                        if (c == y[j]) { S[h][1 + c] += pc; S[h][0] += __logf(se) - (z[c][j] - mx); }          // (the gap first: csrc/loss.hip vx_seg_loss_fwd_k)
                     }
                 }
             }
@@ -649,7 +649,7 @@ __global__ void __launch_bounds__(256) vx_seg_loss_ds_fwd_col_k(VxDs P, const vo
                     for (int c = 0; c < C; ++c) {
                         const float pc = e[c] * inv;
                         S[h][1 + C + c] += pc;
-                        if (c == y[j]) { S[h][1 + c] += pc; S[h][0] += (mx + __logf(se)) - z[c][j]; }
+                        if (c == y[j]) { S[h][1 + c] += pc; S[h][0] += __logf(se) - (z[c][j] - mx); }          // (the gap first: csrc/loss.hip vx_seg_loss_fwd_k)
                     }
                 }
                 }

@@ -146,57 +146,77 @@ __global__ void __launch_bounds__(256) vx_in_bwd_apply_k(const float* __restrict
 // ---------------------------------------------------------------------------------------------
 // channels-first LayerNorm, one thread per voxel (coalesced along V for every channel).
 // ---------------------------------------------------------------------------------------------
-// per-voxel mean / rstd over C with a pivot-shifted single sweep (numerically equivalent to the two-pass form at fp32)
-__device__ __forceinline__ void vx_ln_stats(const float* __restrict__ xb, int C, long V, float eps, float& u, float& r) {
-    const float pivot = xb[0];
-    float s = 0.0f, q = 0.0f;
+// per-voxel mean / rstd over C in two sweeps: the mean first, then the squares centred on the FINISHED mean.  (A single sweep shifted by x[0] forms
+// mean(d^2) - mean(d)^2, which cancels by 1 + (mean - x[0])^2 / var: up to C + 1 when channel 0 is the outlier of its voxel.  The centred form does not
+// depend on where an outlier sits.)  CT > 0: C = CT is known at compile time (16 or 32) and the voxel's channels stay in registers from the first sweep on;
+// CT == 0: any C, every sweep re-reads the column the first one pulled in.  Same serial summation order either way.
+template <int CT, typename F>
+__device__ __forceinline__ void vx_ln_each(int C, F&& f) {
+    if constexpr (CT > 0) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) f(c);
+    } else {
 #pragma unroll 8
-    for (int c = 0; c < C; ++c) { const float d = xb[(long)c * V] - pivot; s += d; q = fmaf(d, d, q); }
-    const float md = s / (float)C;
-    float var = q / (float)C - md * md;
-    var = var < 0.0f ? 0.0f : var;
-    u = pivot + md;
-    r = 1.0f / sqrtf(var + eps);
+        for (int c = 0; c < C; ++c) f(c);
+    }
 }
+template <int CT>
+struct VxLnRow {
+    float xr[CT ? CT : 1];
+    const float* __restrict__ xb;
+    long V;
+    __device__ __forceinline__ float operator()(int c) const { if constexpr (CT > 0) return xr[c]; else return xb[(long)c * V]; }
+    __device__ __forceinline__ void stats(int C, float eps, float& u, float& r) {
+        float s = 0.0f, q = 0.0f;
+        vx_ln_each<CT>(C, [&](int c) { const float t = xb[(long)c * V]; if constexpr (CT > 0) xr[c] = t; s += t; });
+        u = s / (float)C;
+        const float m = u;
+        vx_ln_each<CT>(C, [&](int c) { const float d = (*this)(c) - m; q = fmaf(d, d, q); });
+        r = 1.0f / sqrtf(q / (float)C + eps);
+    }
+};
 
+template <int CT>
 __global__ void __launch_bounds__(256) vx_ln_cf_fwd_k(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      float* __restrict__ out, int C, long V, float eps) {
+                                                      float* __restrict__ out, int Crt, long V, float eps) {
+    const int C = CT ? CT : Crt;
     const long v = (long)blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
-    const float* __restrict__ xb = x + (long)blockIdx.y * C * V + v;
+    VxLnRow<CT> X;
+    X.xb = x + (long)blockIdx.y * C * V + v; X.V = V;
     float* __restrict__ ob = out + (long)blockIdx.y * C * V + v;
     float u, r;
-    vx_ln_stats(xb, C, V, eps, u, r);
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) ob[(long)c * V] = fmaf(gamma[c], (xb[(long)c * V] - u) * r, beta[c]);
+    X.stats(C, eps, u, r);
+    vx_ln_each<CT>(C, [&](int c) { ob[(long)c * V] = fmaf(gamma[c], (X(c) - u) * r, beta[c]); });
 }
 
 // dx = r*(g - mean_c(g) - xhat*mean_c(g*xhat)), g = dout*gamma; per-voxel (mean, rstd) are saved to ws for the parameter pass
+template <int CT>
 __global__ void __launch_bounds__(256) vx_ln_cf_bwd_k(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ dout,
-                                                      float* __restrict__ dx, float* __restrict__ ws, int C, long V, float eps, const float* __restrict__ add) {
+                                                      float* __restrict__ dx, float* __restrict__ ws, int Crt, long V, float eps, const float* __restrict__ add) {
+    const int C = CT ? CT : Crt;
     const long v = (long)blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
     const long base = (long)blockIdx.y * C * V + v;
-    const float* __restrict__ xb = x + base;
+    VxLnRow<CT> X;
+    X.xb = x + base; X.V = V;
     const float* __restrict__ db = dout + base;
     float u, r;
-    vx_ln_stats(xb, C, V, eps, u, r);
+    X.stats(C, eps, u, r);
     float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-        const float xh = (xb[(long)c * V] - u) * r;
+    vx_ln_each<CT>(C, [&](int c) {
+        const float xh = (X(c) - u) * r;
         const float g = db[(long)c * V] * gamma[c];
         s1 += g;
         s2 = fmaf(g, xh, s2);
-    }
+    });
     s1 /= (float)C;
     s2 /= (float)C;
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-        const float xh = (xb[(long)c * V] - u) * r;
+    vx_ln_each<CT>(C, [&](int c) {
+        const float xh = (X(c) - u) * r;
         const float o = r * (db[(long)c * V] * gamma[c] - s1 - xh * s2);
         dx[base + (long)c * V] = add ? add[base + (long)c * V] + o : o;
-    }
+    });
     ws[2 * ((long)blockIdx.y * V + v)] = u;
     ws[2 * ((long)blockIdx.y * V + v) + 1] = r;
 }
@@ -569,8 +589,8 @@ extern "C" int vx_in_bwd_split(const float* dout, const float* y0, const float* 
 // ---------------------------------------------------------------------------------------------------------------------------
 // LayerNorm on FEW voxels with MANY channels (PatchMerging LN over 8C at the 8^3 / 4^3 levels: C = 256..1024, B*V = 256..2048): one thread per
 // voxel walks the channel axis serially with ~B*V threads on the whole chip (81 us for 131 k elements).  Here 16 lanes share one voxel
-// (4 voxels per wave, 16 per block), each lane takes every 16th channel, sums meet in a 16-lane shuffle tree.  Same pivot-shifted
-// single-sweep statistics as vx_ln_stats.
+// (4 voxels per wave, 16 per block), each lane takes every 16th channel, sums meet in a 16-lane shuffle tree.  Same two-sweep
+// statistics as the thread-per-voxel kernels (mean, then squares centred on it).
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int LPV>
 __device__ __forceinline__ float vx_sum_lpv(float v) {
@@ -593,38 +613,44 @@ __global__ void __launch_bounds__(256) vx_ln_cf_lanes_k(const float* __restrict_
     const long vv = live ? vox : 0;
     const long b = vv / V, v = vv % V;
     const float* __restrict__ xb = x + b * C * V + v;
-    const float pivot = xb[0];
+    // the lane's first KR channels stay in registers from the first sweep on (all of them up to C = KR * LPV); the later ones are re-read.  `each` visits the
+    // lane's channels in ascending order in either case
+    constexpr int KR = 8;
+    float xr[KR];
+    auto each = [&](auto&& f) {
+#pragma unroll
+        for (int k = 0; k < KR; ++k) { const int c = sub + k * LPV; if (c < C) f(c, xr[k]); }
+        for (int c = sub + KR * LPV; c < C; c += LPV) f(c, xb[(long)c * V]);
+    };
     float s_ = 0.0f, q_ = 0.0f;
-    for (int c = sub; c < C; c += LPV) { const float d = xb[(long)c * V] - pivot; s_ += d; q_ = fmaf(d, d, q_); }
-    s_ = vx_sum16(s_);
-    q_ = vx_sum16(q_);
-    const float md = s_ / (float)C;
-    float var = q_ / (float)C - md * md;
-    var = var < 0.0f ? 0.0f : var;
-    const float u = pivot + md, r = 1.0f / sqrtf(var + eps);
+#pragma unroll
+    for (int k = 0; k < KR; ++k) { const int c = sub + k * LPV; xr[k] = c < C ? xb[(long)c * V] : 0.0f; }
+    each([&](int, float t) { s_ += t; });
+    const float u = vx_sum16(s_) / (float)C;
+    each([&](int, float t) { const float d = t - u; q_ = fmaf(d, d, q_); });
+    const float r = 1.0f / sqrtf(vx_sum16(q_) / (float)C + eps);
     if (!BWD) {
         float* __restrict__ ob = out + b * C * V + v;
-        if (live)
-            for (int c = sub; c < C; c += LPV) ob[(long)c * V] = fmaf(gamma[c], (xb[(long)c * V] - u) * r, beta[c]);
+        if (live) each([&](int c, float t) { ob[(long)c * V] = fmaf(gamma[c], (t - u) * r, beta[c]); });
     } else {
         const float* __restrict__ db = dout + b * C * V + v;
         float s1 = 0.0f, s2 = 0.0f;
-        for (int c = sub; c < C; c += LPV) {
-            const float xh = (xb[(long)c * V] - u) * r;
+        each([&](int c, float t) {
+            const float xh = (t - u) * r;
             const float g = db[(long)c * V] * gamma[c];
             s1 += g;
             s2 = fmaf(g, xh, s2);
-        }
+        });
         s1 = vx_sum16(s1) / (float)C;
         s2 = vx_sum16(s2) / (float)C;
         if (live) {
             float* __restrict__ ob = out + b * C * V + v;
             const float* __restrict__ ab = beta ? beta + b * C * V + v : nullptr;      // backward: `beta` carries the optional gradient to add (same layout as out)
-            for (int c = sub; c < C; c += LPV) {
-                const float xh = (xb[(long)c * V] - u) * r;
+            each([&](int c, float t) {
+                const float xh = (t - u) * r;
                 const float o = r * (db[(long)c * V] * gamma[c] - s1 - xh * s2);
                 ob[(long)c * V] = ab ? ab[(long)c * V] + o : o;
-            }
+            });
             if (sub == 0) { ws[2 * vv] = u; ws[2 * vv + 1] = r; }
         }
     }
@@ -642,7 +668,10 @@ extern "C" int vx_ln_cf_fwd(const float* x, const float* gamma, const float* bet
         VX_LAUNCH_CHECK("vx_ln_cf_fwd");
         return 0;
     }
-    hipLaunchKernelGGL(vx_ln_cf_fwd_k, dim3(vx_cdiv(V, 256), B), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, out, C, V, eps);
+    const dim3 grid(vx_cdiv(V, 256), B);
+    if (C == 16) vx_ln_cf_fwd_k<16><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, gamma, beta, out, C, V, eps);
+    else if (C == 32) vx_ln_cf_fwd_k<32><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, gamma, beta, out, C, V, eps);
+    else vx_ln_cf_fwd_k<0><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, gamma, beta, out, C, V, eps);
     VX_LAUNCH_CHECK("vx_ln_cf_fwd");
     return 0;
 }
@@ -657,8 +686,9 @@ static int vx_ln_cf_bwd_run(const float* x, const float* gamma, const float* dou
             vx_ln_cf_lanes_k<true, 64><<<dim3(vx_cdiv((long)B * V, 4)), dim3(256), 0, (hipStream_t)stream>>>(x, gamma, add, dout, dx, ws, C, V, (long)B * V, eps);
         else if (vx_ln_use_lanes(B, C, V))
             vx_ln_cf_lanes_k<true><<<dim3(vx_cdiv((long)B * V, 16)), dim3(256), 0, (hipStream_t)stream>>>(x, gamma, add, dout, dx, ws, C, V, (long)B * V, eps);
-        else
-            hipLaunchKernelGGL(vx_ln_cf_bwd_k, dim3(vx_cdiv(V, 256), B), dim3(256), 0, (hipStream_t)stream, x, gamma, dout, dx, ws, C, V, eps, add);
+        else if (C == 16) vx_ln_cf_bwd_k<16><<<dim3(vx_cdiv(V, 256), B), dim3(256), 0, (hipStream_t)stream>>>(x, gamma, dout, dx, ws, C, V, eps, add);
+        else if (C == 32) vx_ln_cf_bwd_k<32><<<dim3(vx_cdiv(V, 256), B), dim3(256), 0, (hipStream_t)stream>>>(x, gamma, dout, dx, ws, C, V, eps, add);
+        else vx_ln_cf_bwd_k<0><<<dim3(vx_cdiv(V, 256), B), dim3(256), 0, (hipStream_t)stream>>>(x, gamma, dout, dx, ws, C, V, eps, add);
     }
     if (parts & 2) {
         VX_REQUIRE(dgamma && dbeta, "vx_ln_cf_bwd: bad pointers");
