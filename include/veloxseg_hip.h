@@ -799,6 +799,34 @@ int vx_hole_scan(const void* lab, int lab_bytes, const int* cc, int N, int D, in
 int vx_hole_fill(const void* lab, void* out, int lab_bytes, const int* cc, int N, const long long* lo, const long long* hi, const int* open, const long long* applied,
                  int n_applied, long V, void* stream);
 
+/* ---- exact Euclidean distance transform and surface-distance gather (csrc/distance.hip) ---------------------------------------------
+ * Reference: medpy.metric.binary.hd95 behind utils/metric/metrics.py: get_hausdorff and utils/metric/metrics_brats.py: HD95 / cal_hd95, i.e.
+ * scipy.ndimage.distance_transform_edt on the host.  One sample per call; masks are packed as in the morphology section (bits[D * H * Wq], tail bits ignored), so
+ * vx_morph_pack -> vx_morph_boundary -> vx_edt_sq chain without an unpack.  Every entry checks pointers, extents, flags and spacings before any launch; a refused
+ * call returns -1 and writes nothing.  No atomics, no cross-workgroup waiting: equal inputs give equal bits.
+ *
+ * Definition, all fp64, every product and sum rounded on its own (no fma):  t_a(d) = fl(fl(d * s_a) * fl(d * s_a));  sq[v] = min over the sites s of
+ * fl(fl(t_z(dz) + t_y(dy)) + t_x(dx)).  Each step is monotone, so three passes along z, y, x give the bits of the brute-force minimum, and sqrt(sq) equals
+ * scipy.ndimage.distance_transform_edt(sampling=(sz, sy, sx)) bit for bit (tests/test_distance_cpu.py).
+ *
+ * vx_edt_max_extent() = 2048, the longest line of a pass: a y tile (every y of a strip of 4 .. 32 x) or an x tile (whole rows) lives in LDS as fp64 and takes at
+ * most 64 KB (65 KB with its line flags), so two workgroups of the largest tile fit the 160 KB of a CU.  vx_edt_grid_cap() = the block count above which every kernel here loops.
+ * vx_edt_sq: sites are the set bits (invert 0) or the clear bits inside the volume (invert 1); the padded tail bits of a row are never sites.  out_sq (D * H * W
+ * doubles) receives the squared distances; no site at all gives +inf everywhere.  Refused: an extent <= 0 or above vx_edt_max_extent(), D * H * W > 2^31 - 1, a
+ * spacing that is not finite or not > 0.  The map lives in out_sq from the first pass on (the y and x passes work in place): there is no workspace.
+ * vx_edt_pass: ONE of the three passes, for measurements and tests: axis 0 (z) reads bits and writes io = t_z or +inf, axis 1 (y) and 2 (x) transform io in place
+ * (bits may be NULL).  vx_edt_sq is pass 0, 1, 2 with (sz, sy, sx).
+ * vx_edt_sqrt: x[i] = the correctly rounded square root of x[i], in place, 1 <= n <= 2^31 - 1.
+ * vx_bits_count: counts[row] = set bits of row (z, y) of a packed mask, D * H ints.  vx_edt_gather: out[offsets[row] + j] = values[row * W + x_j] for the j-th set
+ * bit x_j of the row, i.e. with offsets = the exclusive prefix sum of counts (int64, on the device), the values at the set bits in flat-index order. */
+int vx_edt_max_extent(void);
+int vx_edt_grid_cap(void);
+int vx_edt_sq(const unsigned long long* bits, int invert, double* out_sq, int D, int H, int W, double sz, double sy, double sx, void* stream);
+int vx_edt_pass(int axis, const unsigned long long* bits, int invert, double* io, int D, int H, int W, double spacing, void* stream);
+int vx_edt_sqrt(double* x, long n, void* stream);
+int vx_bits_count(const unsigned long long* bits, int D, int H, int W, int* counts, void* stream);
+int vx_edt_gather(const double* values, const unsigned long long* bits, const long long* offsets, double* out, int D, int H, int W, void* stream);
+
 /* ---- dense strided convolution on MFMA (groups = 1; k odd <= 7, stride 2..4, pad = k / 2): the DownConv layers between the encoder levels and the
  * stem (Encoder.py:29-58, conv_blocks.py:8-27 of the reference).  Implicit GEMM on v_mfma_f32_16x16x4_f32, fp32 in / fp32 accumulate.  ws =
  * vx_conv_mfma_ws_floats(Cin, Cout, K, backward) floats for the operand-order weight image (written by every call).  bwd_data: accumulate = 1 adds

@@ -22,6 +22,7 @@ _CTYPE = {
     "int": ctypes.c_int,
     "long": ctypes.c_long,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
     "unsigned long long": ctypes.c_ulonglong,
 }
 

@@ -2,11 +2,18 @@
 
 `metrics_tensor(gt, pred)` = [FP rate, FN rate, precision, recall, F1, IoU, Dice], each the mean over the batch of the per-sample value
 with the reference's smoothing (1e-5) and float32 arithmetic (utils/metric/metrics.py:44-91).  The per-sample counts come from one
-GPU pass (vx_confusion); the reference instead moves both volumes to the host as IntTensors.  HD95 (medpy) is out of scope.
+GPU pass (vx_confusion); the reference instead moves both volumes to the host as IntTensors.  `get_hausdorff` (HD95) runs on the device
+too (utils/metric/surface.py: medpy's hd95 restated on the exact distance transform of csrc/distance.hip).
 """
 import torch
 
 from ._counts import confusion, to_label_map
+from .surface import reference_hd95
+
+
+def get_hausdorff(gt: torch.Tensor, pred: torch.Tensor, spacing=(1, 1, 1)) -> float:
+    """utils/metric/metrics.py:27-39: nan when gt or pred holds nothing, else medpy's hd95(pred, gt, voxelspacing=spacing) of the (1, 1, D, H, W) masks"""
+    return reference_hd95(gt, pred, spacing)
 
 
 def metrics_tensor(gt: torch.Tensor, pred: torch.Tensor):

@@ -3,10 +3,14 @@
 The reference's `Dice(output, target)` sums over dims (1, 2, 3) of (B, 1, D, H, W) masks, i.e. over (channel, D, H) -- it keeps the
 LAST spatial axis -- and averages `2 (inter + eps) / (sum_o + sum_t + 2 eps)` over all B*W planes (metrics_brats.py:22-27).  That
 per-plane statistic is reproduced exactly: one confusion matrix per (sample, last-axis index) on the GPU, ratio / mean in float32 on the host.
+
+`HD95` and `cal_hd95` (metrics_brats.py:28-57) run on the device as well: utils/metric/surface.py restates medpy's hd95 on the exact distance transform of
+csrc/distance.hip.
 """
 import torch
 
 from ._counts import confusion, to_label_map
+from .surface import reference_hd95
 
 
 def _planes(t: torch.Tensor) -> torch.Tensor:
@@ -49,6 +53,19 @@ def Dice(output: torch.Tensor, target: torch.Tensor, eps=1e-6):
     t = (target != 0).to(torch.uint8)
     conf = confusion(_planes(o), _planes(t), 2)
     return _dice_from(conf[:, 1, 1], conf[:, :, 1].sum(1), conf[:, 1, :].sum(1), eps)
+
+
+def HD95(gt: torch.Tensor, pred: torch.Tensor, spacing=(1, 1, 1)) -> float:
+    """metrics_brats.py:28-39: nan when gt or pred holds nothing, else medpy's hd95(pred, gt, voxelspacing=spacing) of the (1, 1, D, H, W) masks"""
+    return reference_hd95(gt, pred, spacing)
+
+
+def cal_hd95(output: torch.Tensor, target: torch.Tensor, spacing=(1, 1, 1)):
+    """metrics_brats.py:48-57 -> (avg, ET, TC, WT) floats; a region that one side lacks is nan, and so is the average then"""
+    et = HD95(output == 3, target == 3, spacing)
+    tc = HD95((output == 1) | (output == 3), (target == 1) | (target == 3), spacing)
+    wt = HD95(output != 0, target != 0, spacing)
+    return float((et + tc + wt) / 3), float(et), float(tc), float(wt)
 
 
 def show_deep_metrics(outputs, labels, deep=True):

@@ -154,6 +154,20 @@ def key_float(key) -> np.ndarray:
     return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
 
 
+def linear_ranks(n: int, q: float):
+    """numpy's linear percentile rule: -> (virtual index (n - 1) * (q / 100), the two ranks that bracket it)"""
+    v = (n - 1) * (q / 100.0)
+    lo = int(math.floor(v))
+    return v, lo, min(lo + 1, n - 1)
+
+
+def linear_lerp(a, b, v: float, lo: int) -> float:
+    """numpy's _lerp between the order statistics a (rank lo) and b (rank lo + 1) at the virtual index v, in fp64"""
+    a, b, t = np.float64(a), np.float64(b), np.float64(v - lo)
+    diff = b - a
+    return float(b - diff * (1 - t)) if t >= 0.5 else float(a + diff * t)
+
+
 class IntensityStatistics:
     """The reference's CT foreground statistics (preprocess/normalization_CT_PET.py:65-81) without gathering the voxels: exact min / max / order statistics by radix
     select over the order-preserving 32-bit keys, mean / std in two fp64 passes over the union of the selected voxels (mask > 0).
@@ -235,11 +249,10 @@ class IntensityStatistics:
             mm = d["minmax"].cpu().numpy().view(np.uint32)
             self.min, self.max = (float(v) for v in key_float(mm))
             # numpy's linear rule: virtual index (n - 1) * (q / 100), the order statistics at its floor and floor + 1
-            self._virtual = {q: (n - 1) * (q / 100.0) for q in self.percentiles}
+            self._virtual = {q: linear_ranks(n, q)[0] for q in self.percentiles}
             ranks = set()
-            for v in self._virtual.values():
-                lo = int(math.floor(v))
-                ranks.update((lo, min(lo + 1, n - 1)))
+            for q in self.percentiles:
+                ranks.update(linear_ranks(n, q)[1:])
             self._rank = {r: (0, r) for r in sorted(ranks)}          # rank -> (key prefix so far, rank inside that prefix)
             counts = {0: n}
         else:
@@ -278,12 +291,10 @@ class IntensityStatistics:
         return self._values[rank]
 
     def percentile(self, q: float) -> float:
-        v = self._virtual[float(q)]
-        lo = int(math.floor(v))
-        a, b = np.float64(self.order_statistic(lo)), np.float64(self.order_statistic(min(lo + 1, self.n - 1)))
-        t = np.float64(v - lo)
-        diff = b - a
-        return float(b - diff * (1 - t)) if t >= 0.5 else float(a + diff * t)          # numpy's _lerp
+        if float(q) not in self._virtual:
+            raise KeyError(float(q))
+        v, lo, hi = linear_ranks(self.n, float(q))
+        return linear_lerp(self.order_statistic(lo), self.order_statistic(hi), v, lo)
 
     def result(self):
         if not self.done:
