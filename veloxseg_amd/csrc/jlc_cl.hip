@@ -6,8 +6,8 @@
 //   channels (CG = 8) or 2 taps x 16 channels (CG = 16).  Taps are ordered centre-first: index 0..26 = the 3^3 centre in K = 3 order, 27 = padding, 28..125 = the 98
 //   outer taps of the 5^3 cube, so the K = 3 product is the first 7 / 14 steps of the same operand stream and K = 1 is the step holding tap 13.
 //   B operand: the group's input volume with its halo, channels-last in LDS as two fp16 pieces of x * 2^ex (ex from the block's own maximum): one ds_read_b128 per
-//   piece, voxel and step.  A operand: per-group weight images in operand order (two fp16 pieces of w * 2^ew, ew per (group, kernel size)), streamed from L2 with a
-//   two-deep register FIFO.  Products hi*hi + hi*lo + lo*hi (22 mantissa bits), fp32 accumulation, exact rescale by 2^-(ex+ew).
+//   piece, voxel and step.  A operand: per-group weight images in operand order (two fp16 pieces of w * 2^ew, ew per (group, kernel size)), streamed from L2 through a
+//   register ring of VX_CL_RING entries that is primed before the staging and runs across the three kernel sizes (cl_stream).  Products hi*hi + hi*lo + lo*hi (22 mantissa bits), fp32 accumulation, exact rescale by 2^-(ex+ew).
 //   forward  : y1, y3, y5 + bias and the per-(b, c) partial sums (sum, sum of squares) the InstanceNorm statistics need (one slot per wave)
 //   backward : dx = conv5^T(g5) + conv3^T(g3) + conv1^T(g1) + d_o: the same stream with the transposed images, three halos (pad 2 / 1 / 0), offsets negated
 // A block = 4 waves = one (sample, group) and a chunk of 4 x TPW voxel tiles; every block stages the whole group volume (<= 16 KB of input).
@@ -59,6 +59,11 @@ constexpr ClTaps cl_make_taps() {
 }
 __constant__ ClTaps cl_taps = cl_make_taps();
 
+// Depth of the register ring the weight operands stream through (entries of 9 registers).  0 = the whole K = 3 + K = 1 stream plus 8.  Chosen on the training step, not
+// on the kernels alone.
+#ifndef VX_CL_RING
+#define VX_CL_RING 8
+#endif
 template <int CG> struct ClK {
     static constexpr int TPS = 32 / CG;                 // taps per MFMA step
     static constexpr int NS5 = CG == 8 ? 32 : 63;       // steps of the K = 5 stream (126 taps)
@@ -66,6 +71,7 @@ template <int CG> struct ClK {
     static constexpr int S1 = 13 / TPS;                 // the step holding the centre tap
     static constexpr int NE = NS5 + NS3 + 1;            // image entries per group and direction
     static constexpr int NH = CG / 8;                   // 8-channel halves of a voxel's channel vector (one LDS array each)
+    static constexpr int R = VX_CL_RING > 0 ? VX_CL_RING : NS3 + 1 + 8;      // depth of the operand ring (cl_stream)
 };
 
 // ------------------------------------------------------------------------------------------------------------------ weight images
@@ -139,61 +145,126 @@ struct VxCl {
     int B, C, G, D, H, W, V, NT, nchunk;
     ClHalo h5, h3, h1;
 };
-// one group volume (CG channels x V voxels, channel stride V) -> LDS, channels-last, two fp16 pieces of v * 2^e with e from the block's maximum.  dst: [piece][half][npos] x 16 B,
-// zero borders.  Returns e.  (Two passes over the input: the second one hits L1 / L2.)
+// Staging of one group volume (CG channels x V voxels, channel stride V) -> LDS, channels-last, two fp16 pieces of v * 2^e with e from the block's maximum.
+// dst: [piece][half][npos] x 16 B, zero borders.  The volume is read from global memory ONCE: item i = (channel half, voxel) of thread i % 256 stays in registers
+// (2 NH items of 8 floats: V <= 512) between the maximum and the conversion, so every load of the block -- the volumes, the weight ring -- is in flight together
+// and the padded image is zeroed while they are.
+template <int CG> struct ClVol { float x[2 * (CG / 8)][8]; };
 template <int CG>
-__device__ __forceinline__ int cl_stage(unsigned char* __restrict__ dst, const float* __restrict__ src, const VxCl& p, const ClHalo& hl, float* __restrict__ red) {
+__device__ __forceinline__ void cl_vol_load(ClVol<CG>& r, const float* __restrict__ src, const VxCl& p) {
     constexpr int NH = CG / 8;
-    float mx = 0.0f;
-    for (int i = threadIdx.x; i < CG * p.V / 4; i += 256) {
-        const float4 v = reinterpret_cast<const float4*>(src)[i];
-        mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-    }
-    for (int i = CG * p.V / 4 * 4 + threadIdx.x; i < CG * p.V; i += 256) mx = fmaxf(mx, fabsf(src[i]));
-    mx = vx_wave_max(mx);
-    __syncthreads();                          // (red may still be read from the previous call)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    const int nz = 2 * NH * hl.npos;          // zero everything (borders), 16 bytes per item
-    for (int i = threadIdx.x; i < nz; i += 256) reinterpret_cast<cl_u4*>(dst)[i] = (cl_u4){0u, 0u, 0u, 0u};
-    __syncthreads();
-    const int e = cl_exp16(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
-    const float sc = ldexpf(1.0f, e);
-    for (int i = threadIdx.x; i < NH * p.V; i += 256) {
-        const int half = i / p.V, v = i - half * p.V;
-        const int w = v % p.W, hh = (v / p.W) % p.H, d = v / (p.W * p.H);
-        float x[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = src[(long)(8 * half + j) * p.V + v] * sc;
-        uint32_t h[4], l[4];
+    for (int k = 0; k < 2 * NH; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        const int half = (NH == 2 && i >= p.V) ? 1 : 0, v = i - half * p.V;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cl_split2(x[2 * q], x[2 * q + 1], h[q], l[q]);
-        const int hp = ((d + hl.P) * hl.HH + (hh + hl.P)) * hl.HW + (w + hl.P);
-        reinterpret_cast<cl_u4*>(dst)[half * hl.npos + hp] = (cl_u4){h[0], h[1], h[2], h[3]};
-        reinterpret_cast<cl_u4*>(dst)[(NH + half) * hl.npos + hp] = (cl_u4){l[0], l[1], l[2], l[3]};
+        for (int j = 0; j < 8; ++j) r.x[k][j] = 0.0f;
+        if (i < NH * p.V) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r.x[k][j] = src[(long)(8 * half + j) * p.V + v];
+        }
     }
-    return e;
 }
-// acc[t] += A(entry e0 + s) x B(voxel tile t, taps of step s0 + s), s = 0 .. ns-1.  xs: this lane's base in the staged volume (its channel half); hp[t]: byte offset of
-// the lane's voxel; toff: byte offsets of the taps in the volume's geometry; sign = +1 forward / -1 backward.
+__device__ __forceinline__ void cl_zero(unsigned char* __restrict__ dst, int n16) {          // n16 items of 16 bytes
+    for (int i = threadIdx.x; i < n16; i += 256) reinterpret_cast<cl_u4*>(dst)[i] = (cl_u4){0u, 0u, 0u, 0u};
+}
+template <int CG>
+__device__ __forceinline__ float cl_vol_max(const ClVol<CG>& r) {
+    float mx = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 2 * (CG / 8); ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(r.x[k][j]));
+    return vx_wave_max(mx);
+}
+template <int CG>
+__device__ __forceinline__ void cl_vol_store(unsigned char* __restrict__ dst, const ClVol<CG>& r, const VxCl& p, const ClHalo& hl, int e) {
+    constexpr int NH = CG / 8;
+    const float sc = ldexpf(1.0f, e);
+#pragma unroll
+    for (int k = 0; k < 2 * NH; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        if (i < NH * p.V) {
+            const int half = (NH == 2 && i >= p.V) ? 1 : 0, v = i - half * p.V;
+            const int w = v % p.W, hh = (v / p.W) % p.H, d = v / (p.W * p.H);
+            uint32_t h[4], l[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cl_split2(r.x[k][2 * q] * sc, r.x[k][2 * q + 1] * sc, h[q], l[q]);
+            const int hp = ((d + hl.P) * hl.HH + (hh + hl.P)) * hl.HW + (w + hl.P);
+            reinterpret_cast<cl_u4*>(dst)[half * hl.npos + hp] = (cl_u4){h[0], h[1], h[2], h[3]};
+            reinterpret_cast<cl_u4*>(dst)[(NH + half) * hl.npos + hp] = (cl_u4){l[0], l[1], l[2], l[3]};
+        }
+    }
+}
+
+// The A operand stream of a wave: the NE image entries of its group (K = 5 steps, K = 3 steps, the K = 1 step) through a register ring of R entries -- the (hi, lo)
+// operands and the step's tap offset -- that runs across the K5 -> K3 -> K1 boundaries.  cl_ring_prime requests the first R entries (before the staging, whose
+// latency they share); cl_stream walks the entries in order, refills the slot it frees with entry e + R and keeps the B operands (LDS) one entry ahead.  Entries past
+// NE are never requested, so R may exceed what is left.  Entry order, and the three products per tile and entry, are those of the weight image: hi*hi, hi*lo, lo*hi.
+template <int R> struct ClRing { cl_u4 h[R], l[R]; int off[R]; };
+template <int TPW> struct ClSeg { const unsigned char* xs; int lo_off; int hp[TPW]; const int* toff; int sign; };      // staged volume of a kernel size (lane's channel half), piece stride, voxel offsets, tap table
+template <int CG>
+__device__ __forceinline__ void cl_ring_prime(ClRing<ClK<CG>::R>& rg, const cl_u4* __restrict__ img) {
+    using KK = ClK<CG>;
+#pragma unroll
+    for (int j = 0; j < KK::R; ++j)
+        if (j < KK::NE) { rg.h[j] = img[(long)j * 128]; rg.l[j] = img[(long)j * 128 + 64]; }
+}
+template <int CG> __device__ __forceinline__ constexpr int cl_entry_seg(int e) { return e < ClK<CG>::NS5 ? 0 : (e < ClK<CG>::NS5 + ClK<CG>::NS3 ? 1 : 2); }
 template <int CG, int TPW>
-__device__ __forceinline__ void cl_accum(cl_f4 (&acc)[TPW], const cl_u4* __restrict__ img, int ns, int s0, const unsigned char* __restrict__ xs, int lo_off,
-                                         const int (&hp)[TPW], const int* __restrict__ toff, int sign, int Gl) {
-    cl_u4 ah = img[0], al = img[64];
-#pragma unroll 2
-    for (int s = 0; s < ns; ++s) {
-        cl_u4 nh = ah, nl = al;
-        if (s + 1 < ns) { nh = img[(long)(s + 1) * 128]; nl = img[(long)(s + 1) * 128 + 64]; }
-        const int tap = CG == 8 ? 4 * (s0 + s) + Gl : 2 * (s0 + s) + (Gl >> 1);
-        const int off = sign * toff[tap];
+__device__ __forceinline__ int cl_entry_off(int e, const ClSeg<TPW> (&sg)[3], int Gl) {
+    using KK = ClK<CG>;
+    const int c = cl_entry_seg<CG>(e);
+    const int s = c == 0 ? e : (c == 1 ? e - KK::NS5 : KK::S1);
+    const int tap = CG == 8 ? 4 * s + Gl : 2 * s + (Gl >> 1);
+    return sg[c].sign == 0 ? 0 : sg[c].sign * sg[c].toff[tap];
+}
+// done(c, acc): called after the last entry of kernel size c (0, 1, 2 = K 5, 3, 1) with its accumulators, which then restart from zero
+template <int CG, int TPW, class F>
+__device__ __forceinline__ void cl_stream(ClRing<ClK<CG>::R>& rg, const cl_u4* __restrict__ img, const ClSeg<TPW> (&sg)[3], int Gl, F&& done) {
+    using KK = ClK<CG>;
+    constexpr int R = KK::R, NE = KK::NE;
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+        if (j < NE) rg.off[j] = cl_entry_off<CG, TPW>(j, sg, Gl);
+    constexpr int BA = 2;          // the B operands (LDS) run BA entries ahead of the MFMAs (BA < R: their offsets are in the ring)
+    static_assert(R > BA, "the ring holds the offsets of the B operands in flight");
+    cl_f4 acc[TPW];
+    cl_u4 bh[BA + 1][TPW], bl[BA + 1][TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) acc[t] = (cl_f4){0.f, 0.f, 0.f, 0.f};
+    auto read_b = [&](int e) {          // (e: a constant once the loops are unrolled)
+        const int c = cl_entry_seg<CG>(e), o = rg.off[e % R];
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-            const cl_u4 bh = *reinterpret_cast<const cl_u4*>(xs + hp[t] + off);
-            const cl_u4 bl = *reinterpret_cast<const cl_u4*>(xs + lo_off + hp[t] + off);
-            acc[t] = CL_MFMA(ah, bh, acc[t]);
-            acc[t] = CL_MFMA(ah, bl, acc[t]);
-            acc[t] = CL_MFMA(al, bh, acc[t]);
+            bh[e % (BA + 1)][t] = *reinterpret_cast<const cl_u4*>(sg[c].xs + sg[c].hp[t] + o);
+            bl[e % (BA + 1)][t] = *reinterpret_cast<const cl_u4*>(sg[c].xs + sg[c].lo_off + sg[c].hp[t] + o);
         }
-        ah = nh; al = nl;
+    };
+#pragma unroll
+    for (int e = 0; e < BA; ++e)
+        if (e < NE) read_b(e);
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int j = e % R, c = cl_entry_seg<CG>(e);
+        __builtin_amdgcn_sched_barrier(0);          // (the loop is unrolled: without these the scheduler hoists requests past the ring, and R no longer bounds the registers)
+        if (e + BA < NE) read_b(e + BA);
+        const cl_u4 ah = rg.h[j], al = rg.l[j];
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+            acc[t] = CL_MFMA(ah, bh[e % (BA + 1)][t], acc[t]);
+            acc[t] = CL_MFMA(ah, bl[e % (BA + 1)][t], acc[t]);
+            acc[t] = CL_MFMA(al, bh[e % (BA + 1)][t], acc[t]);
+        }
+        if (e + R < NE) {          // the freed slot takes entry e + R
+            rg.h[j] = img[(long)(e + R) * 128]; rg.l[j] = img[(long)(e + R) * 128 + 64];
+            rg.off[j] = cl_entry_off<CG, TPW>(e + R, sg, Gl);
+        }
+        if (e + 1 == NE || cl_entry_seg<CG>(e + 1) != c) {
+            done(c, acc);
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) acc[t] = (cl_f4){0.f, 0.f, 0.f, 0.f};
+        }
     }
 }
 __device__ __forceinline__ void cl_fill_toff(int* __restrict__ toff, const ClHalo& hl) {
@@ -211,8 +282,19 @@ __global__ void __launch_bounds__(256) vx_jlc_cl_fwd_k(const float* __restrict__
     unsigned char* __restrict__ xs = cl_lds + 1024;
     const int chunk = blockIdx.x, bg = blockIdx.y, b = bg / p.G, g = bg - b * p.G;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, Gl = lane >> 4;
+    const bool has_tile = (chunk * 4 + wave) * TPW < p.NT;          // (a wave without a tile still takes part in every barrier)
+    const cl_u4* __restrict__ ig = img + ((long)g * KK::NE) * 128 + lane;
     cl_fill_toff(toff, p.h5);
-    const int ex = cl_stage<CG>(xs, x + ((long)b * p.C + (long)g * CG) * p.V, p, p.h5, red);
+    ClRing<KK::R> rg;
+    if (has_tile) cl_ring_prime<CG>(rg, ig);
+    ClVol<CG> vol;
+    cl_vol_load<CG>(vol, x + ((long)b * p.C + (long)g * CG) * p.V, p);
+    cl_zero(xs, 2 * KK::NH * p.h5.npos);
+    const float wmx = cl_vol_max<CG>(vol);
+    if (lane == 0) red[wave] = wmx;
+    __syncthreads();
+    const int ex = cl_exp16(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+    cl_vol_store<CG>(xs, vol, p, p.h5, ex);
     __syncthreads();
     const int half_off = (CG == 16 ? (Gl & 1) : 0) * p.h5.npos * 16, lo_off = KK::NH * p.h5.npos * 16;
     int hp[TPW], pv[TPW];
@@ -228,11 +310,18 @@ __global__ void __launch_bounds__(256) vx_jlc_cl_fwd_k(const float* __restrict__
     cl_f4 a5[TPW], a3[TPW], a1[TPW];
 #pragma unroll
     for (int t = 0; t < TPW; ++t) { a5[t] = (cl_f4){0.f, 0.f, 0.f, 0.f}; a3[t] = a5[t]; a1[t] = a5[t]; }
-    const cl_u4* __restrict__ ig = img + ((long)g * KK::NE) * 128 + lane;
-    if ((chunk * 4 + wave) * TPW < p.NT) {
-        cl_accum<CG, TPW>(a5, ig, KK::NS5, 0, xs + half_off, lo_off, hp, toff, 1, Gl);
-        cl_accum<CG, TPW>(a3, ig + (long)KK::NS5 * 128, KK::NS3, 0, xs + half_off, lo_off, hp, toff, 1, Gl);
-        cl_accum<CG, TPW>(a1, ig + (long)(KK::NS5 + KK::NS3) * 128, 1, KK::S1, xs + half_off, lo_off, hp, toff, 1, Gl);
+    if (has_tile) {
+        ClSeg<TPW> sg[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            sg[c].xs = xs + half_off; sg[c].lo_off = lo_off; sg[c].toff = toff; sg[c].sign = 1;
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) sg[c].hp[t] = hp[t];
+        }
+        cl_stream<CG, TPW>(rg, ig, sg, Gl, [&](int c, const cl_f4 (&acc)[TPW]) {
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) { if (c == 0) a5[t] = acc[t]; else if (c == 1) a3[t] = acc[t]; else a1[t] = acc[t]; }
+        });
     }
     // ---- results: lane (voxel n of the tile, output channels 4 Gl + i); per-(b, c) partial sums of this wave
     const float f5 = ldexpf(1.0f, -(ex + (int)esc[g * 3 + 0])), f3 = ldexpf(1.0f, -(ex + (int)esc[g * 3 + 1])), f1 = ldexpf(1.0f, -(ex + (int)esc[g * 3 + 2]));
@@ -277,18 +366,34 @@ __global__ void __launch_bounds__(256) vx_jlc_cl_bwd_k(const float* __restrict__
     extern __shared__ __attribute__((aligned(16))) unsigned char cl_lds[];
     int* __restrict__ toff5 = reinterpret_cast<int*>(cl_lds);                 // [128]
     int* __restrict__ toff3 = toff5 + 128;                                    // [128] (the 3^3 centre in the pad-1 geometry)
-    float* __restrict__ red = reinterpret_cast<float*>(cl_lds + 1024);        // [4]
+    float* __restrict__ red = reinterpret_cast<float*>(cl_lds + 1024);        // [3][4]
     unsigned char* __restrict__ x5 = cl_lds + 2048;
     unsigned char* __restrict__ x3 = x5 + (size_t)2 * KK::NH * p.h5.npos * 16;
     unsigned char* __restrict__ x1 = x3 + (size_t)2 * KK::NH * p.h3.npos * 16;
     const int chunk = blockIdx.x, bg = blockIdx.y, b = bg / p.G, g = bg - b * p.G;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, Gl = lane >> 4;
+    const bool has_tile = (chunk * 4 + wave) * TPW < p.NT;
+    const cl_u4* __restrict__ ig = img + ((long)(p.G + g) * KK::NE) * 128 + lane;          // (direction 1)
     cl_fill_toff(toff5, p.h5);
     cl_fill_toff(toff3, p.h3);
+    ClRing<KK::R> rg;
+    if (has_tile) cl_ring_prime<CG>(rg, ig);
+    // g5, g3 and g1 in one phase: all loads in flight together, one barrier pair for the three maxima, one conversion pass
     const long gbase = ((long)b * p.C + (long)g * CG) * p.V;
-    const int e5 = cl_stage<CG>(x5, g5 + gbase, p, p.h5, red);
-    const int e3 = cl_stage<CG>(x3, g3 + gbase, p, p.h3, red);
-    const int e1 = cl_stage<CG>(x1, g1 + gbase, p, p.h1, red);
+    ClVol<CG> v5, v3, v1;
+    cl_vol_load<CG>(v5, g5 + gbase, p);
+    cl_vol_load<CG>(v3, g3 + gbase, p);
+    cl_vol_load<CG>(v1, g1 + gbase, p);
+    cl_zero(x5, 2 * KK::NH * (p.h5.npos + p.h3.npos + p.h1.npos));          // (the three images are contiguous)
+    const float m5 = cl_vol_max<CG>(v5), m3 = cl_vol_max<CG>(v3), m1 = cl_vol_max<CG>(v1);
+    if (lane == 0) { red[wave] = m5; red[4 + wave] = m3; red[8 + wave] = m1; }
+    __syncthreads();
+    const int e5 = cl_exp16(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+    const int e3 = cl_exp16(fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
+    const int e1 = cl_exp16(fmaxf(fmaxf(red[8], red[9]), fmaxf(red[10], red[11])));
+    cl_vol_store<CG>(x5, v5, p, p.h5, e5);
+    cl_vol_store<CG>(x3, v3, p, p.h3, e3);
+    cl_vol_store<CG>(x1, v1, p, p.h1, e1);
     __syncthreads();
     const int hsel = CG == 16 ? (Gl & 1) : 0;
     int hp5[TPW], hp3[TPW], hp1[TPW], pv[TPW];
@@ -303,37 +408,24 @@ __global__ void __launch_bounds__(256) vx_jlc_cl_bwd_k(const float* __restrict__
         hp3[t] = (((d + 1) * p.h3.HH + (hh + 1)) * p.h3.HW + (w + 1)) * 16;
         hp1[t] = ((d * p.h1.HH + hh) * p.h1.HW + w) * 16;
     }
-    cl_f4 acc[TPW], tot[TPW];
+    cl_f4 tot[TPW];
 #pragma unroll
     for (int t = 0; t < TPW; ++t) tot[t] = (cl_f4){0.f, 0.f, 0.f, 0.f};
-    const cl_u4* __restrict__ ig = img + ((long)(p.G + g) * KK::NE) * 128 + lane;          // (direction 1)
-    if ((chunk * 4 + wave) * TPW < p.NT) {
-        {
-            const float f = ldexpf(1.0f, -(e5 + (int)esc[g * 3 + 0]));
+    if (has_tile) {
+        const float f5 = ldexpf(1.0f, -(e5 + (int)esc[g * 3 + 0])), f3 = ldexpf(1.0f, -(e3 + (int)esc[g * 3 + 1])), f1 = ldexpf(1.0f, -(e1 + (int)esc[g * 3 + 2]));
+        // (K = 1, pad 0: the centre tap's offset is 0 in every geometry and the other taps of its step have zero weights; their addresses stay inside x1 only if the
+        //  offsets are not applied: sign 0 reads the lane's own voxel for every tap of the step)
+        ClSeg<TPW> sg[3];
+        sg[0].xs = x5 + hsel * p.h5.npos * 16; sg[0].lo_off = KK::NH * p.h5.npos * 16; sg[0].toff = toff5; sg[0].sign = -1;
+        sg[1].xs = x3 + hsel * p.h3.npos * 16; sg[1].lo_off = KK::NH * p.h3.npos * 16; sg[1].toff = toff3; sg[1].sign = -1;
+        sg[2].xs = x1 + hsel * p.h1.npos * 16; sg[2].lo_off = KK::NH * p.h1.npos * 16; sg[2].toff = toff3; sg[2].sign = 0;
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) acc[t] = (cl_f4){0.f, 0.f, 0.f, 0.f};
-            cl_accum<CG, TPW>(acc, ig, KK::NS5, 0, x5 + hsel * p.h5.npos * 16, KK::NH * p.h5.npos * 16, hp5, toff5, -1, Gl);
-#pragma unroll
-            for (int t = 0; t < TPW; ++t) tot[t] += acc[t] * f;
-        }
-        {
-            const float f = ldexpf(1.0f, -(e3 + (int)esc[g * 3 + 1]));
-#pragma unroll
-            for (int t = 0; t < TPW; ++t) acc[t] = (cl_f4){0.f, 0.f, 0.f, 0.f};
-            cl_accum<CG, TPW>(acc, ig + (long)KK::NS5 * 128, KK::NS3, 0, x3 + hsel * p.h3.npos * 16, KK::NH * p.h3.npos * 16, hp3, toff3, -1, Gl);
+        for (int t = 0; t < TPW; ++t) { sg[0].hp[t] = hp5[t]; sg[1].hp[t] = hp3[t]; sg[2].hp[t] = hp1[t]; }
+        cl_stream<CG, TPW>(rg, ig, sg, Gl, [&](int c, const cl_f4 (&acc)[TPW]) {
+            const float f = c == 0 ? f5 : (c == 1 ? f3 : f1);
 #pragma unroll
             for (int t = 0; t < TPW; ++t) tot[t] += acc[t] * f;
-        }
-        {
-            const float f = ldexpf(1.0f, -(e1 + (int)esc[g * 3 + 2]));
-#pragma unroll
-            for (int t = 0; t < TPW; ++t) acc[t] = (cl_f4){0.f, 0.f, 0.f, 0.f};
-            // (pad 0: the centre tap's offset is 0 in every geometry -- toff5[13] = 0 -- and the other taps of the step have zero weights; their addresses stay inside x1
-            //  only if they are not applied: the step reads with the offsets of toff1 = all zero)
-            cl_accum<CG, TPW>(acc, ig + (long)(KK::NS5 + KK::NS3) * 128, 1, KK::S1, x1 + hsel * p.h1.npos * 16, KK::NH * p.h1.npos * 16, hp1, toff3 + 27, 0, Gl);
-#pragma unroll
-            for (int t = 0; t < TPW; ++t) tot[t] += acc[t] * f;
-        }
+        });
     }
     if (4 * Gl < CG) {
 #pragma unroll
