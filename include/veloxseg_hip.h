@@ -788,6 +788,17 @@ int vx_morph_step(const unsigned long long* in, unsigned long long* out, unsigne
                   int border_value, void* stream);
 int vx_morph_boundary(const unsigned long long* in, unsigned long long* out, int D, int H, int W, int connectivity, void* stream);
 int vx_morph_unpack(const unsigned long long* bits, const void* in, void* out, int lab_bytes, long value, int mode, int D, int H, int W, void* stream);
+/* The ball: dilation / erosion by a structuring element given in millimetres, i.e. as a compact list of its rows.  rows[i] (a device array of
+ * n_rows ints, 1 <= n_rows <= vx_morph_ball_max_rows() = 4096: the list is staged in 16 KB of LDS) holds a signed 8-bit dz in bits 0 - 7, a signed 8-bit dy in bits
+ * 8 - 15 and hw = 0 .. 63 in bits 16 - 21: the offsets (dz, dy, dx) with |dx| <= hw.  Rows the element does not have are not listed.  The entry cannot read the list;
+ * the kernel is memory-safe for ANY contents: it uses hw & 63, takes dz and dy as their 8 bits say and bounds-checks every read, so a row that points outside the
+ * volume reads border_value.  op 0: out[v] = OR over the listed offsets o of in[v + o]; op 1: the AND.  Voxels outside the volume read border_value; tail bits are
+ * ignored on input (of in and of gate) and zero on output.  gate (may be NULL): out = result & gate, and a word whose gate word is 0 costs one read and one write --
+ * the surface-overlap counts of utils/metric/surface.py run it with both operands surfaces.  out differs from in and from gate; gate may be in.  Refused before any
+ * launch: a null in / out / rows, bad extents, n_rows outside 1 .. max, op or border_value outside {0, 1}, out aliasing in or gate. */
+int vx_morph_ball_max_rows(void);
+int vx_morph_ball(const unsigned long long* in, const unsigned long long* gate, unsigned long long* out, int D, int H, int W, const int* rows, int n_rows, int op,
+                  int border_value, void* stream);
 /* Hole filling (MONAI's FillHoles restated; for a {0, 1} map scipy.ndimage.binary_fill_holes): vx_morph_background writes bg = (lab == 0) as uint8, the input of
  * vx_cc_label, whose map cc (ids 1..N on the background) the next two read.  vx_hole_scan: the caller sets lo[0..N] = INT64_MAX, hi[0..N] = INT64_MIN, open[0..N]
  * = 0; for every background voxel, open[id] = 1 if a neighbour lies outside the volume, and the values of its in-volume neighbours with lab != 0 go into lo[id]

@@ -60,6 +60,69 @@ __global__ void __launch_bounds__(256) vx_mo_step_k(const vx_u64* __restrict__ i
     }
 }
 
+// ---- the ball: a structuring element given as a compact list of rows (dz, dy, hw), each the interval |dx| <= hw ------------------------------
+#define VX_MO_BALL_ROWS 4096         // records one call takes: the list lives in LDS, 16 KB
+
+// OR over k = 0 .. n of the 128-bit value (hi : lo) >> k, its low word; 1 <= n <= 63.  By doubling: after the loop acc holds the shifts 0 .. s - 1, s the largest power
+// of two <= n + 1, and one more shift by n + 1 - s (< s) covers the rest.  Every shift count is in 1 .. 63.  A shift of the pair by at most 63 in total moves nothing
+// above bit 126 into the low word, so the zeros that enter hi from above never reach it.
+__device__ __forceinline__ vx_u64 vx_mo_spread_down(vx_u64 hi, vx_u64 lo, int n) {
+    const int m = n + 1;
+    int s = 1;
+    for (; 2 * s <= m; s *= 2) {
+        lo |= (lo >> s) | (hi << (64 - s));
+        hi |= hi >> s;
+    }
+    const int t = m - s;
+    if (t > 0) lo |= (lo >> t) | (hi << (64 - t));
+    return lo;
+}
+
+// the mirror image: OR over k = 0 .. n of (hi : lo) << k, its HIGH word (hi = the word itself, lo = the word left of it)
+__device__ __forceinline__ vx_u64 vx_mo_spread_up(vx_u64 hi, vx_u64 lo, int n) {
+    const int m = n + 1;
+    int s = 1;
+    for (; 2 * s <= m; s *= 2) {
+        hi |= (hi << s) | (lo >> (64 - s));
+        lo |= lo << s;
+    }
+    const int t = m - s;
+    if (t > 0) hi |= (hi << t) | (lo >> (64 - t));
+    return hi;
+}
+
+// One thread per output word, the record list staged once per block in LDS.  Every lane is on the same record, so hw and the trip counts of the spread are uniform.
+// Nothing in a record is trusted: hw is masked to 0 .. 63, dz and dy are whatever their 8 bits say, and every fetch is bounds-checked (vx_mo_fetch).  Written as a
+// dilation; an erosion is the complement form of vx_mo_step_k.  A word stops reading rows once every bit the caller asked for (the gate, or the whole word) is set:
+// the gated form between two surfaces reads almost nothing.
+__global__ void __launch_bounds__(256) vx_mo_ball_k(const vx_u64* __restrict__ in, const vx_u64* gate, vx_u64* __restrict__ out, int D, int H, int Wq, vx_u64 tail,
+                                                    vx_u64 inv, vx_u64 bfill, const int* __restrict__ rows, int n_rows) {
+    __shared__ int rec[VX_MO_BALL_ROWS];
+    for (int k = threadIdx.x; k < n_rows; k += 256) rec[k] = rows[k];
+    __syncthreads();
+    const long nw = (long)D * H * Wq;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nw; i += (long)gridDim.x * 256) {
+        const unsigned u = (unsigned)i, rowi = u / (unsigned)Wq;
+        const int q = (int)(u % (unsigned)Wq), y = (int)(rowi % (unsigned)H), z = (int)(rowi / (unsigned)H);
+        vx_u64 want = q == Wq - 1 ? tail : ~0ull;
+        if (gate) want &= gate[i];
+        if (want == 0ull) { out[i] = 0ull; continue; }
+        vx_u64 acc = 0ull;          // (of the complement for an erosion: a bit set here is a bit cleared in the result)
+        for (int k = 0; k < n_rows; ++k) {
+            const int r = rec[k], hw = (r >> 16) & 63;
+            const int zz = z + (int)(signed char)(r & 0xff), yy = y + (int)(signed char)((r >> 8) & 0xff);
+            const vx_u64 c = vx_mo_fetch(in, zz, yy, q, D, H, Wq, tail, inv, bfill);
+            if (hw == 0) acc |= c;
+            else {
+                const vx_u64 l = vx_mo_fetch(in, zz, yy, q - 1, D, H, Wq, tail, inv, bfill), rr = vx_mo_fetch(in, zz, yy, q + 1, D, H, Wq, tail, inv, bfill);
+                if ((l | c | rr) != 0ull) acc |= vx_mo_spread_down(rr, c, hw) | vx_mo_spread_up(c, l, hw);
+            }
+            if ((acc & want) == want) break;
+        }
+        out[i] = (acc ^ inv) & want;
+    }
+}
+
 // one wave per word: its ballot over 64 consecutive voxels of a row IS the word.  A wave takes VX_MO_PACK_U consecutive words per trip.
 template <typename T>
 __global__ void __launch_bounds__(256) vx_mo_pack_k(const T* __restrict__ lab, T value, int match, vx_u64* __restrict__ bits, long rows, int W, int Wq) {
@@ -251,6 +314,23 @@ extern "C" int vx_morph_boundary(const unsigned long long* in, unsigned long lon
     const int Wq = vx_mo_wq(W);
     vx_mo_step_k<<<dim3(vx_mo_grid(((long)D * H * Wq + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(in, out, D, H, Wq, vx_mo_tail(W), ~0ull, ~0ull, connectivity, 1);
     VX_LAUNCH_CHECK("vx_morph_boundary");
+    return 0;
+}
+
+extern "C" int vx_morph_ball_max_rows(void) { return VX_MO_BALL_ROWS; }
+
+extern "C" int vx_morph_ball(const unsigned long long* in, const unsigned long long* gate, unsigned long long* out, int D, int H, int W, const int* rows, int n_rows, int op,
+                             int border_value, void* stream) {
+    VX_REQUIRE(in && out && rows, "vx_morph_ball: null pointer");
+    VX_REQUIRE(out != in && out != gate, "vx_morph_ball: out must be neither in nor gate");
+    VX_REQUIRE(vx_mo_extents_ok(D, H, W), "vx_morph_ball: bad sizes %d x %d x %d (each > 0, D * H * W <= 2^31 - 1)", D, H, W);
+    VX_REQUIRE(n_rows >= 1 && n_rows <= VX_MO_BALL_ROWS, "vx_morph_ball: %d rows, 1 .. %d wanted", n_rows, VX_MO_BALL_ROWS);
+    VX_REQUIRE(op == 0 || op == 1, "vx_morph_ball: op %d is neither 0 (dilate) nor 1 (erode)", op);
+    VX_REQUIRE(border_value == 0 || border_value == 1, "vx_morph_ball: border_value %d is neither 0 nor 1", border_value);
+    const int Wq = vx_mo_wq(W);
+    vx_mo_ball_k<<<dim3(vx_mo_grid(((long)D * H * Wq + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(in, gate, out, D, H, Wq, vx_mo_tail(W), op ? ~0ull : 0ull,
+                                                                                                       (border_value ^ op) ? ~0ull : 0ull, rows, n_rows);
+    VX_LAUNCH_CHECK("vx_morph_ball");
     return 0;
 }
 

@@ -8,12 +8,18 @@ too (utils/metric/surface.py: medpy's hd95 restated on the exact distance transf
 import torch
 
 from ._counts import confusion, to_label_map
-from .surface import reference_hd95
+from .surface import reference_hd95, reference_surface_dice
 
 
 def get_hausdorff(gt: torch.Tensor, pred: torch.Tensor, spacing=(1, 1, 1)) -> float:
     """utils/metric/metrics.py:27-39: nan when gt or pred holds nothing, else medpy's hd95(pred, gt, voxelspacing=spacing) of the (1, 1, D, H, W) masks"""
     return reference_hd95(gt, pred, spacing)
+
+
+def get_surface_dice(gt: torch.Tensor, pred: torch.Tensor, threshold, spacing=(1, 1, 1)) -> float:
+    """the normalised surface Dice of nnU-Net's evaluator at `threshold` millimetres, with get_hausdorff's conventions: nan when gt or pred holds nothing, else
+    normalized_surface_dice(pred, gt, threshold, spacing) (utils/metric/surface.py).  The reference has no counterpart in this module."""
+    return reference_surface_dice(gt, pred, threshold, spacing)
 
 
 def metrics_tensor(gt: torch.Tensor, pred: torch.Tensor):
