@@ -702,6 +702,54 @@ int vx_blur_batch(const void* records, int n_records, float* tmp, int D, int H, 
 #define VX_AFFINE_RECORD_BYTES 144
 int vx_affine_batch(const void* records, int n_records, int Do, int Ho, int Wo, void* stream);
 
+/* ---- elastic deformation (csrc/augment_elastic.hip): a device-drawn smooth displacement field and the affine resampler with a displacement ----
+ * A FIELD is three contiguous fp32 planes of V = Do*Ho*Wo elements, the displacement along D, H and W of every OUTPUT voxel; n fields are 3 n contiguous planes.
+ *
+ * vx_elastic_noise fills n_planes contiguous planes at `out` with uniforms in [-1, 1).  Plane j belongs to field j / 3; `keys` is a DEVICE table of ceil(n_planes / 3)
+ * uint64 keys, one per field.  Element e = (j % 3) * V + flat index of the voxel takes word e & 3 of the Philox4x32-7 words r[0..3] of (key of the field, stream
+ * VX_ELASTIC_STREAM, counter e >> 2), and u = (float)((int)(r >> 8) - 8388608) * 2^-23: a multiple of 2^-23, exact in fp32.  One launch, whatever n_planes; equal keys
+ * give equal bits.  Checked before the launch (-1, nothing written): keys and out non-null, keys 8-byte and out 4-byte aligned, n_planes > 0, V > 0; -3 when the
+ * blocks exceed one grid.
+ *
+ * vx_elastic_smooth: separable Gaussian smoothing of n_planes contiguous (D, H, W) planes with zero padding outside the plane.  `weights` is a DEVICE table of
+ * ceil(n_planes / 3) records of VX_ELASTIC_WEIGHT_BYTES bytes, one per FIELD (its three planes and their three axes share it):
+ *   byte   0  int32   tail, 0 <= tail <= VX_ELASTIC_MAX_TAIL (a field whose tail is outside that range writes nothing)
+ *   byte   4  float[VX_ELASTIC_MAX_TAIL + 1]  w_0 .. w_tail: the centre and ONE half of the symmetric vector
+ * Passes W, H, D, each output rounded to fp32 before the next; in a pass y = w_0 x_0 + sum_{k = 1 .. tail} w_k (x_-k + x_+k), k ascending, the pair added first, x = 0
+ * outside the plane (vx_blur_batch's rule).  W pass: `planes` -> `result`; H pass: `result` -> `planes`; D pass: `planes` -> `result`.  On return `result` holds the
+ * smoothed planes and `planes` holds scratch (the H pass).  Three launches per call, whatever n_planes.  A line and its halo are staged in LDS: the W pass takes
+ * VX_ELASTIC_ROWS rows x VX_ELASTIC_TILE_W outputs per block, the H and D passes VX_ELASTIC_STRIP consecutive x by VX_ELASTIC_TILE_LINE outputs along the axis, so
+ * global accesses run along W and an input element is read once per pass (plus the halo where an axis is longer than one tile).  Checked before any launch (-1,
+ * nothing written): pointers non-null, table 8-byte and planes 4-byte aligned, `planes` and `result` not overlapping, n_planes > 0, positive extents; -3 when a plane
+ * has 2^31 voxels or more or the blocks exceed one grid.
+ * vx_elastic_smooth_pass is ONE of those passes (axis 0 = D, 1 = H, 2 = W; `planes` -> `result`, `planes` unchanged) with the same checks and axis in 0..2: the
+ * kernel vx_elastic_smooth runs for that axis.  tools/elastic_probe.py times the passes through it.
+ *
+ * vx_elastic_batch is vx_affine_batch with a displacement.  A record is VX_ELASTIC_RECORD_BYTES bytes:
+ *   byte   0  the VX_AFFINE_RECORD_BYTES bytes of an affine record, same offsets, same meaning
+ *   byte 144  uint64  device pointer to a contiguous (3, Do, Ho, Wo) fp32 field (4-byte aligned; shared by every key and channel of a sample, never written), or 0
+ *   byte 152  float   magnitude m;  bytes 156..159 unused
+ * Rule: the displacement moves the centred OUTPUT coordinate before the matrix (MONAI's order: grid += smooth(offset) * magnitude, then the affine grid), every
+ * operation rounded to fp32 on its own:
+ *   p_a = (float)o_a - 0.5f * (float)(Out_a - 1);   p'_a = p_a + m * u_a[o];   s_a = ((A[a][0] * p'_0 + A[a][1] * p'_1) + A[a][2] * p'_2) + c_a
+ * and from s_a on everything is vx_affine_batch's rule (the same device code).  A record whose field pointer is 0 gives the bytes vx_affine_batch gives for its first
+ * 144 bytes.  A non-finite p'_a (from a non-finite field only) is the caller's to avoid; it reads inside [lo, hi] all the same.  Checks and refusals are those of
+ * vx_affine_batch: -1 (nothing written) for a null or misaligned table, n_records <= 0 or a non-positive extent, -3 for an output volume of 2^31 voxels or more or
+ * blocks beyond one grid; a record the host should not have sent (unknown type, mode or pad, trilinear on an integer type, lo > hi, a null source or destination, a
+ * stride beyond 32 bits) writes nothing. */
+#define VX_ELASTIC_STREAM 0x454C4153544943ull        /* "ELASTIC": not VX_AUG_NOISE_STREAM, and far above every dropout site id */
+#define VX_ELASTIC_MAX_TAIL 48
+#define VX_ELASTIC_WEIGHT_BYTES 200
+#define VX_ELASTIC_RECORD_BYTES 160
+#define VX_ELASTIC_ROWS 8
+#define VX_ELASTIC_TILE_W 256
+#define VX_ELASTIC_STRIP 32
+#define VX_ELASTIC_TILE_LINE 256
+int vx_elastic_noise(const void* keys, int n_planes, long V, float* out, void* stream);
+int vx_elastic_smooth(const void* weights, int n_planes, float* planes, float* result, int D, int H, int W, void* stream);
+int vx_elastic_smooth_pass(const void* weights, int n_planes, const float* planes, float* result, int axis, int D, int H, int W, void* stream);
+int vx_elastic_batch(const void* records, int n_records, int Do, int Ho, int Wo, void* stream);
+
 /* ---- volume preprocessing (csrc/preprocess.hip): foreground z-score, CT clip + normalise, dataset order statistics, separable resampling -----------------
  * Reference: preprocess/normalization_MRI.py:7-12,52, preprocess/normalization_CT_PET.py:6-11,23-31,65-81, utils/inference_extern_mri.py:73-75,95.
  * Volumes are fp32 contiguous, indexed with `long`; masks / labels are uint8 / int32 / int64 / fp32 (bytes code 1 / 4 / 8 / -4, as in vx_label_chunk_count),

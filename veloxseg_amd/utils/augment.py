@@ -7,7 +7,9 @@ Beyond the reference's three: RandFlipd, RandScaleIntensityd, RandShiftIntensity
 RandAffined / affine_sample / affine_matrix: rotation about all three axes, scale and translation of every sample, key and channel in ONE kernel call
 (csrc/augment_affine.hip); spatial_from_config reads train_config["spatial_augment"].
 RandGaussianSmoothd / RandScaleIntensityFixedMeand / RandAdjustContrastd / blur_separable: a separable blur and the transforms that need a channel's min / max /
-mean / std, whose statistics are reduced on the device and read there by the step program (csrc/augment_blur.hip, csrc/augment_stats.hip)."""
+mean / std, whose statistics are reduced on the device and read there by the step program (csrc/augment_blur.hip, csrc/augment_stats.hip).
+Rand3DElasticd / elastic_field / elastic_sample: a smooth random displacement field drawn and smoothed on the device from one host seed per sample, and the affine
+resampler with that displacement in front of its matrix (csrc/augment_elastic.hip); the elastic_* keys of train_config["spatial_augment"]."""
 import math
 
 import numpy as np
@@ -1191,14 +1193,274 @@ class RandAffined(_Randomizable):
         return outs
 
 
-_SPATIAL_KEYS = ("rotate_degrees", "scale", "translate", "prob", "padding_mode", "context")
+# ---- elastic deformation: a device-drawn smooth displacement field and the resampler with a displacement (csrc/augment_elastic.hip) --------
+# Modelled on MONAI 1.x (Rand3DElastic: uniform offsets in [-1, 1), GaussianFilter(sigma, truncated=3) with zero padding, grid += offset * magnitude, then the affine
+# grid) and UNPINNED against MONAI itself, which is not installed; tests/elastic_ref.py restates the noise, the weights, the rule and the draw order.
+ELASTIC_RECORD_BYTES, ELASTIC_WEIGHT_BYTES, ELASTIC_MAX_TAIL, ELASTIC_MAX_SIGMA = 160, 200, 48, 16.0
+ELASTIC_STREAM = 0x454C4153544943          # VX_ELASTIC_STREAM of include/veloxseg_hip.h ("ELASTIC")
+ELASTIC_ROWS, ELASTIC_TILE_W, ELASTIC_STRIP, ELASTIC_TILE_LINE = 8, 256, 32, 256          # the tiles of vx_elastic_smooth (the header's constants of the same names)
+_ELA = np.dtype([("aff", _AFF), ("field", "<u8"), ("m", "<f4"), ("unused", "<i4")])
+_ELW = np.dtype([("tail", "<i4"), ("w", "<f4", (ELASTIC_MAX_TAIL + 1,))])
+assert (_ELA.itemsize, _ELW.itemsize) == (ELASTIC_RECORD_BYTES, ELASTIC_WEIGHT_BYTES)
+
+
+def elastic_weights(sigma):
+    """fp32 half vector w_0 .. w_tail of MONAI's gaussian_1d(sigma, truncated=3, approx="erf"): tail = int(max(3 sigma, 0.5) + 0.5), gaussian_weights' formula, formed in
+    fp64 and rounded once; not normalised.  0 < sigma <= 16 (tail <= 48)."""
+    sigma = float(sigma)
+    if not (math.isfinite(sigma) and 0.0 < sigma <= ELASTIC_MAX_SIGMA):
+        raise ValueError(f"sigma {sigma!r} outside (0, {ELASTIC_MAX_SIGMA}]: the weight table holds a tail of at most {ELASTIC_MAX_TAIL}")
+    tail = int(max(3.0 * sigma, 0.5) + 0.5)
+    t = 1.0 / (sigma * math.sqrt(2.0))
+    return np.array([0.5 * (math.erf((k + 0.5) * t) - math.erf((k - 0.5) * t)) for k in range(tail + 1)], dtype=np.float64).astype(np.float32)
+
+
+def _elastic_field_plan(shape, seeds, sigmas, out):
+    """every check of elastic_field -> (shape, uint64 keys, the weight records, out); nothing touches the GPU but the allocation"""
+    try:
+        shape = tuple(int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"elastic_field: shape {shape!r} must be three positive extents") from None
+    if len(shape) != 3 or any(v <= 0 for v in shape) or shape[0] * shape[1] * shape[2] > _INT_MAX:
+        raise ValueError(f"elastic_field: shape {shape!r} must be three positive extents, below 2^31 voxels")
+    seeds, sigmas = list(seeds), list(sigmas)
+    if not seeds or len(seeds) != len(sigmas):
+        raise ValueError(f"elastic_field: {len(seeds)} seeds and {len(sigmas)} sigmas: one of each per field, at least one field")
+    keys = np.zeros(len(seeds), dtype="<u8")
+    for i, s in enumerate(seeds):
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < 1 << 64:
+            raise ValueError(f"elastic_field: seed {s!r} of field {i} must be an integer in [0, 2^64)")
+        keys[i] = int(s)
+    wts = np.zeros(len(seeds), dtype=_ELW)
+    for r, s in zip(wts, sigmas):
+        w = elastic_weights(s)
+        r["tail"], r["w"][:w.size] = w.size - 1, w
+    want = (len(seeds), 3) + shape
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == want):
+        raise ValueError(f"elastic_field: `out` must be a contiguous float32 {want} CUDA tensor")
+    if not torch.cuda.is_available():
+        raise RuntimeError("elastic_field: the HIP path needs a CUDA (ROCm) device; there is no CPU fallback")
+    return shape, keys, wts, out
+
+
+def _elastic_pack(entries, out_size, out):
+    """every check of elastic_sample -> (the record table as a numpy array of _ELA, the destinations, out_size): the affine part of an entry goes through _affine_pack
+    (every check of affine_sample, the overlap of destinations and sources among them) and its 144 bytes are taken as they come"""
+    entries = [tuple(e) for e in entries]
+    try:
+        size = tuple(int(v) for v in out_size)
+    except (TypeError, ValueError):
+        size = ()
+    mags = []
+    for i, e in enumerate(entries):                                  # what the record adds to an affine record first: none of it needs a device
+        if len(e) not in (7, 8):
+            raise ValueError(f"elastic_sample: entry {i} has {len(e)} fields (source, matrix, mode, padding_mode, cval, field, magnitude[, bounds])")
+        field = e[5]
+        try:
+            mags.append(float(e[6]))
+        except (TypeError, ValueError):
+            raise ValueError(f"elastic_sample: entry {i}: magnitude {e[6]!r} is not a number") from None
+        if not math.isfinite(mags[-1]):
+            raise ValueError(f"elastic_sample: entry {i}: magnitude {mags[-1]!r} is not finite")
+        if field is None:
+            continue
+        if not isinstance(field, torch.Tensor):
+            raise TypeError(f"elastic_sample: entry {i}: the field must be a tensor or None, got {type(field).__name__}")
+        if field.dtype != torch.float32:
+            raise TypeError(f"elastic_sample: entry {i}: field dtype {field.dtype} not supported (float32)")
+        if tuple(field.shape) != (3,) + size or not field.is_contiguous():
+            raise ValueError(f"elastic_sample: entry {i}: the field must be a contiguous {(3,) + size} tensor, got {tuple(field.shape)} with strides {field.stride()}")
+        if not field.is_cuda:
+            raise RuntimeError(f"elastic_sample: entry {i}: the field must be a CUDA (ROCm) tensor; there is no CPU fallback")
+    table, out, out_size = _affine_pack([e[:5] + e[7:] for e in entries], out_size, out)
+    tab = np.zeros(len(entries), dtype=_ELA)
+    tab["aff"] = table.numpy().view(_AFF)
+    tab["m"] = mags
+    writes = [(o.data_ptr(), o.data_ptr() + o.numel() * o.element_size()) for o in out]
+    checked = set()
+    for i, (e, r) in enumerate(zip(entries, tab)):
+        field = e[5]
+        if field is None:
+            continue
+        if field.device != e[0].device:
+            raise ValueError(f"elastic_sample: entry {i}: the field lives on {field.device}, the source on {e[0].device}")
+        r["field"] = field.data_ptr()
+        if field.data_ptr() not in checked:                      # (the keys and channels of a sample share their field)
+            checked.add(field.data_ptr())
+            lo, hi = field.data_ptr(), field.data_ptr() + field.numel() * 4
+            for j, (wa, wb) in enumerate(writes):
+                if wa < hi and lo < wb:
+                    raise ValueError(f"elastic_sample: the destination of entry {j} overlaps the field of entry {i}: field and destination alias")
+    return tab, out, out_size
+
+
+def _elastic_run(field_plan, sample_plan, dev):
+    """ONE table (the records, the keys, the weight records), ONE upload, then vx_elastic_noise + vx_elastic_smooth for the fields of `field_plan` (or None) and
+    vx_elastic_batch for the records of `sample_plan` (or None); `field_plan` carries its result tensor"""
+    n_rec = 0 if sample_plan is None else len(sample_plan[0])
+    n_field = 0 if field_plan is None else len(field_plan[1])
+    off_keys = n_rec * ELASTIC_RECORD_BYTES
+    off_wts = off_keys + n_field * 8
+    host = np.zeros(off_wts + n_field * ELASTIC_WEIGHT_BYTES, dtype=np.uint8)
+    if n_rec:
+        host[:off_keys] = sample_plan[0].view(np.uint8).reshape(-1)
+    if n_field:
+        host[off_keys:off_wts] = field_plan[1].view(np.uint8)
+        host[off_wts:] = field_plan[2].view(np.uint8).reshape(-1)
+        scratch = torch.empty_like(field_plan[3])
+    table = torch.from_numpy(host).to(dev)
+    base, stream = table.data_ptr(), H.stream_ptr()
+    if n_field:
+        shape, result = field_plan[0], field_plan[3]
+        H.call("vx_elastic_noise", base + off_keys, 3 * n_field, shape[0] * shape[1] * shape[2], scratch.data_ptr(), stream)
+        H.call("vx_elastic_smooth", base + off_wts, 3 * n_field, scratch.data_ptr(), result.data_ptr(), *shape, stream)
+    if n_rec:
+        H.call("vx_elastic_batch", base, n_rec, *sample_plan[2], stream)
+
+
+def elastic_field(shape, seeds, sigmas, out=None):
+    """n smooth random displacement fields -> a (n, 3, D, H, W) float32 CUDA tensor: uniforms in [-1, 1) drawn on the DEVICE (Philox4x32-7 of (seeds[i], ELASTIC_STREAM),
+    element e = plane * D*H*W + flat voxel index: include/veloxseg_hip.h) and smoothed with elastic_weights(sigmas[i]) along W, H and D with zero padding; one sigma for
+    the three planes and axes of a field.  ONE vx_elastic_noise call and ONE vx_elastic_smooth call for all n fields, one table upload.  `out`: the tensor to write
+    (contiguous float32), else it is allocated.  Everything is checked before any GPU work; there is no CPU fallback (RuntimeError without a device)."""
+    shape, keys, wts, out = _elastic_field_plan(shape, seeds, sigmas, out)
+    if out is None:
+        out = torch.empty((len(keys), 3) + shape, dtype=torch.float32, device="cuda")
+    _elastic_run((shape, keys, wts, out), None, out.device)
+    return out
+
+
+def elastic_sample(entries, out_size, out=None):
+    """affine_sample with a displacement.  entries: [(source, matrix, mode, padding_mode, cval, field, magnitude[, bounds])]; `field`: a contiguous (3, Do, Ho, Wo) float32
+    CUDA tensor (elastic_field's; the keys and channels of a sample share one) or None, `magnitude` a finite number: the centred output coordinate p becomes
+    p + magnitude * field[:, o] BEFORE the matrix (MONAI's order); everything else is affine_sample's, checks included, and an entry whose field is None gives the bytes
+    affine_sample gives.  No destination may overlap a source or a field.  ONE table, ONE upload, ONE call of vx_elastic_batch; no CPU fallback."""
+    tab, out, out_size = _elastic_pack(entries, out_size, out)
+    _elastic_run(None, (tab, out, out_size), out[0].device)
+    return out
+
+
+def _pair_range(v, what, top=None):
+    """a number v -> (v, v); a pair -> (min, max); finite"""
+    if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool):
+        lo = hi = float(v)
+    else:
+        try:
+            pair = [float(t) for t in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} {v!r}: a number or a pair of numbers") from None
+        if len(pair) != 2:
+            raise ValueError(f"{what} {v!r}: a number or a pair of numbers")
+        lo, hi = (min(pair), max(pair)) if all(math.isfinite(t) for t in pair) else (float("nan"),) * 2
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f"{what} {v!r} is not finite")
+    if top is not None and not (0.0 < lo and hi <= top):
+        raise ValueError(f"{what} {v!r} outside (0, {top}]: the weight table holds a tail of at most {ELASTIC_MAX_TAIL}")
+    return lo, hi
+
+
+class Rand3DElasticd(RandAffined):
+    """MONAI Rand3DElasticd(keys, sigma_range, magnitude_range, prob, rotate_range, scale_range, translate_range, spatial_size, mode, padding_mode) without shear, plus
+    RandAffined's cval and context: a smooth random displacement of every output voxel, then RandAffined's matrix.  The field is elastic_field(patch shape, seed,
+    sigma); a voxel samples the source at A (p + magnitude * field) + c (elastic_sample).  sigma in voxels, at most 16.
+    Draw order (modelled on MONAI 1.x, unpinned against MONAI itself; tests/elastic_ref.py restates it): one RandomState; every sample draws R.rand() < prob FIRST and,
+    ONLY IF that fires, seed = R.randint(2**31 - 1), magnitude = R.uniform(*magnitude_range), sigma = R.uniform(*sigma_range), then RandAffined's nine uniforms in its
+    order.  The seed stands where MONAI draws the 3 D H W uniforms of the field itself on the host: the field comes from the DEVICE generator under that seed, so the
+    field, and every draw after it, differ from MONAI's.
+    On a list of samples: one table, one upload, ONE vx_elastic_noise, ONE vx_elastic_smooth and ONE vx_elastic_batch call for every fired sample, key and channel;
+    a sample that does not fire keeps its tensors (or is resampled with the identity when spatial_size differs from its shape).  `last_draws`: what the last call
+    drew, one entry per sample, None or (seed, magnitude, sigma, rotate[3], translate[3], scale[3]).
+    Not implemented: shear, a coarse control grid with spline up-sampling (batchgenerators' newer form), low-resolution simulation."""
+
+    def __init__(self, keys, sigma_range, magnitude_range, prob=0.1, rotate_range=None, scale_range=None, translate_range=None, spatial_size=None, mode="bilinear",
+                 padding_mode="border", cval=0.0, context=False):
+        super().__init__(keys, prob=prob, rotate_range=rotate_range, scale_range=scale_range, translate_range=translate_range, spatial_size=spatial_size, mode=mode,
+                         padding_mode=padding_mode, cval=cval, context=context)
+        self.sigma_range = _pair_range(sigma_range, "sigma_range", ELASTIC_MAX_SIGMA)
+        self.magnitude_range = _pair_range(magnitude_range, "magnitude_range")
+        self.last_draws = None
+
+    def draw(self):
+        """-> None (the sample does not fire) or (seed, magnitude, sigma, rotate[3], translate[3], scale[3])"""
+        if not self.R.rand() < self.prob:
+            return None
+        seed = int(self.R.randint(2 ** 31 - 1))
+        mag = float(self.R.uniform(low=self.magnitude_range[0], high=self.magnitude_range[1]))
+        sigma = float(self.R.uniform(low=self.sigma_range[0], high=self.sigma_range[1]))
+        rot = [float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.rotate_range]
+        tra = [float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.translate_range]
+        sca = [1.0 + float(self.R.uniform(low=lo, high=hi)) for lo, hi in self.scale_range]
+        return seed, mag, sigma, rot, tra, sca
+
+    def __call__(self, data):
+        if not isinstance(data, list):
+            return self([data])[0]
+        outs, plans, fired, out_size, dev = [], [], [], self.spatial_size, None
+        self.last_draws = []
+        for i, d in enumerate(data):
+            params = self.draw()
+            self.last_draws.append(params)
+            out = dict(d)
+            outs.append(out)
+            if params is None and self.spatial_size is None:
+                continue
+            for k in self.keys:
+                _need_cuda(d[k], f"Rand3DElasticd[{k!r}]")
+            shapes = {tuple(d[k].shape[1:]) for k in self.keys}
+            if len(shapes) != 1:
+                raise ValueError(f"Rand3DElasticd: sample {i}: keys of different spatial shapes {sorted(shapes)}")
+            shape = shapes.pop()
+            size = self.spatial_size or shape
+            if params is None and size == shape:
+                continue
+            if out_size is None:
+                out_size = size
+            if size != out_size:
+                raise ValueError(f"Rand3DElasticd: sample {i} has the patch shape {shape}, the call {out_size}: set spatial_size")
+            bounds = None
+            if self.context:
+                if "crop_start" not in d or "crop_source_shape" not in d:
+                    raise ValueError("Rand3DElasticd(context=True) needs `crop_start` and `crop_source_shape` in every sample: crop with RandCropByPosNegLabeld(copy=False)")
+                start, parent = [int(v) for v in d["crop_start"]], [int(v) for v in d["crop_source_shape"]]
+                bounds = ([-s for s in start], [p - 1 - s for p, s in zip(parent, start)])
+            dev = d[self.keys[0]].device if dev is None else dev
+            m = affine_matrix() if params is None else affine_matrix(rotate=params[3], scale=params[5], translate=params[4])
+            if params is not None:
+                fired.append(params)
+            plans.append((out, d, m, bounds, None if params is None else (len(fired) - 1, params[1])))
+        if not plans:
+            return outs
+        field_plan = fields = None
+        if fired:
+            shape, keys, wts, _ = _elastic_field_plan(out_size, [p[0] for p in fired], [p[2] for p in fired], None)
+            fields = torch.empty((len(fired), 3) + shape, dtype=torch.float32, device=dev)
+            field_plan = (shape, keys, wts, fields)
+        entries, slots = [], []
+        for out, d, m, bounds, el in plans:
+            field, mag = (None, 0.0) if el is None else (fields[el[0]], el[1])
+            for k, mode in zip(self.keys, self.mode):
+                t = d[k]
+                for ch in range(t.shape[0]):
+                    entries.append((t[ch], m, mode, self.padding_mode, self.cval, field, mag) + (() if bounds is None else (bounds,)))
+                slots.append((out, k, t.shape[0], t.dtype, t.device))
+        dests = [torch.empty((c,) + out_size, dtype=dt, device=dv) for _, _, c, dt, dv in slots]
+        tab, flat, out_size = _elastic_pack(entries, out_size, [v[ch] for v in dests for ch in range(v.shape[0])])
+        _elastic_run(field_plan, (tab, flat, out_size), dev)
+        for (out, k, _, _, _), v in zip(slots, dests):
+            out[k] = v
+        return outs
+
+
+_SPATIAL_KEYS = ("rotate_degrees", "scale", "translate", "prob", "padding_mode", "context", "elastic_sigma", "elastic_magnitude")
+_ELASTIC_DEFAULTS = {"elastic_sigma": (5.0, 13.0), "elastic_magnitude": (100.0, 200.0)}          # the other key's value when only one of the two is given
 
 
 def spatial_from_config(cfg, keys, modes):
     """train_config["spatial_augment"] -> RandAffined.  Keys (all optional; an unknown key raises ValueError): rotate_degrees (a number: that range about each of the
     three axes; or three values, about D, H, W), scale (a number or three: the scale is 1 + U(-v, v) per axis), translate (voxels, a number or three), prob (default
     0.5, the chain's rotation probability), padding_mode ("border" default, or "constant"), context (default False: with it the crop hands views over and the
-    sampler reads the volume around the patch)."""
+    sampler reads the volume around the patch).  With elastic_sigma and / or elastic_magnitude (each a number or a (low, high) pair; voxels, sigma at most 16; the one
+    left out takes (5, 13) / (100, 200)) -> Rand3DElasticd with the same affine ranges, prob, padding_mode and context."""
     if not isinstance(cfg, dict):
         raise ValueError(f"spatial_augment config must be a dict, got {type(cfg).__name__}")
     unknown = sorted(set(cfg) - set(_SPATIAL_KEYS))
@@ -1212,9 +1474,13 @@ def spatial_from_config(cfg, keys, modes):
         if len(vals) != 3:
             raise ValueError(f"spatial_augment config: {what} {v!r}: a number or three values")
         return [f(t) for t in vals]
-    return RandAffined(keys, prob=cfg.get("prob", 0.5), rotate_range=per_axis(cfg.get("rotate_degrees"), "rotate_degrees", rotation_range_from_degrees),
-                       scale_range=per_axis(cfg.get("scale"), "scale"), translate_range=per_axis(cfg.get("translate"), "translate"), mode=modes,
-                       padding_mode=cfg.get("padding_mode", "border"), context=bool(cfg.get("context", False)))
+    kw = dict(prob=cfg.get("prob", 0.5), rotate_range=per_axis(cfg.get("rotate_degrees"), "rotate_degrees", rotation_range_from_degrees),
+              scale_range=per_axis(cfg.get("scale"), "scale"), translate_range=per_axis(cfg.get("translate"), "translate"), mode=modes,
+              padding_mode=cfg.get("padding_mode", "border"), context=bool(cfg.get("context", False)))
+    if cfg.get("elastic_sigma") is None and cfg.get("elastic_magnitude") is None:
+        return RandAffined(keys, **kw)
+    el = {k: cfg[k] if cfg.get(k) is not None else v for k, v in _ELASTIC_DEFAULTS.items()}
+    return Rand3DElasticd(keys, sigma_range=el["elastic_sigma"], magnitude_range=el["elastic_magnitude"], **kw)
 
 
 class Compose:
